@@ -1,6 +1,7 @@
 """Headline benchmark: inner-loop images/sec of the Reptile/FOMAML adaptation loop over EfficientLab-6-3 (224x224, 5-shot).
 
     python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (+ what the last timed step computed, DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Launch contract: for N > 1 the launcher (torch.distributed.run) exports RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; this process
@@ -22,9 +23,8 @@ import re
 import sys
 import time
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); concurrent task lanes (--concurrent-tasks)
-# want one queue each next to torch's own streams.  Read when the HIP runtime loads, so set before `import torch`.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# (HIP multiplexes a process's streams onto the hardware queues the environment grants it; the number of queues is left to the
+# environment.  Concurrent task lanes (--concurrent-tasks) then share those queues: same results, less overlap when there are fewer.)
 
 import torch
 
@@ -68,7 +68,12 @@ def parse(argv=None):
     ap.add_argument("--pool", type=int, default=8, help="number of distinct synthetic tasks resident per GPU")
     ap.add_argument("--cpu-baseline-from", default=None,
                     help="N > 1 lines do not time the CPU oracle; carry `cpu_baseline` by value from this N = 1 bench line (a JSON file, e.g. BENCH_rNN.json)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed meta-step left its caller (the model's variables, the loss) as DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1 (ms_per_step is the time of one timed step)")
+    return a
 
 
 def _free_port():
@@ -504,6 +509,35 @@ def batchnorm_hbm(L, calls, dll, flush_bytes):
     return fams
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(L, loss, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what a caller of the timed path holds after its last meta-step -- the learner's global variables under their TF
+    names (trainables, BN moving statistics, the Adam slots with --adam: what a checkpoint stores, Learner.named_numpy) and the loss of
+    that step's last inner step -- as out_dir/<name>.npy, '/' of the names as '.', float32 (integer scalars float64).  Above max_bytes
+    in all, every array keeps the same fraction of its elements, a sample (sorted flat indices) drawn from a generator seeded by its name,
+    so two builds of the project dump the same elements."""
+    import zlib
+    import numpy as np
+    arrays = {name.replace("/", "."): np.asarray(v, dtype=np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+              for name, v in L.named_numpy().items()}
+    arrays["loss"] = np.asarray([loss], dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = total > max_bytes
+    if sampled:
+        frac = (max_bytes - 8 * len(arrays)) / float(total)     # (headroom: an array never keeps fewer than one element)
+        for name, a in arrays.items():
+            n = max(int(a.size * frac), 1)
+            if n < a.size:
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                arrays[name] = a.reshape(-1)[np.sort(rng.choice(a.size, size=n, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": sum(a.nbytes for a in arrays.values()), "sampled": sampled}
+
+
 def main():
     import contextlib
     argv = sys.argv[1:]
@@ -606,6 +640,9 @@ def _run(args):
     imgs_per_task = ((args.inner_iters - 1) * args.inner_batch + 5) if args.foml else args.inner_iters * args.inner_batch
     value = world * args.tasks_per_gpu * imgs_per_task * args.steps / dt
     loss = L.loss_value()
+    dumped = None
+    if rank == 0 and args.dump_outputs:     # before the roofline pass below, whose eager inner steps move the learner's state on
+        dumped = dump_outputs(L, loss, args.dump_outputs)
 
     roof = dwr = fam = bnr = None
     native = None
@@ -670,6 +707,8 @@ def _run(args):
             out["fp32_native_note"] = native["note"]
         if cpu is not None:
             out["gpu_over_cpu"] = value / cpu["value"]
+        if dumped is not None:
+            out["dump_outputs"] = dumped
     else:
         out = None
     if world > 1:

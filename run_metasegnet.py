@@ -20,9 +20,8 @@ import os
 import random
 import sys
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); concurrent task lanes (--concurrent-tasks)
-# want one queue each next to torch's own streams.  Read when the HIP runtime loads, so set before `import torch`.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# (HIP multiplexes a process's streams onto the hardware queues the environment grants it; the number of queues is left to the
+# environment.  Concurrent task lanes (--concurrent-tasks) then share those queues: same results, less overlap when there are fewer.)
 
 import numpy as np
 import torch

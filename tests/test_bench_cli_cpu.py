@@ -108,3 +108,66 @@ def test_cpu_baseline_follows_the_protocol_of_baseline_md():
     out = b.cpu_baseline(args)
     assert out["kind"] == "port" and out["cores"] >= 1 and out["value"] > 0
     assert "after 3 warm-up steps" in out["sample"] and out["sample"].startswith("4 inner SGD steps = 2 tasks")
+
+
+def test_steps_below_one_are_refused():
+    """ms_per_step is the time of one timed step: `--steps 0` has none to report."""
+    b = _bench()
+    assert b.parse(["--steps", "3"]).steps == 3
+    with pytest.raises(SystemExit) as e:
+        b.parse(["--steps", "0"])
+    assert e.value.code == 2
+
+
+class _StubLearner:
+    def __init__(self, named):
+        self.named = named
+
+    def named_numpy(self):
+        return {k: v.copy() for k, v in self.named.items()}
+
+
+def _named(seed=0):
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    return {"net/blocks_0/conv2d/kernel": rng.randn(3, 3, 8, 16).astype(np.float32),
+            "net/blocks_0/tpu_batch_normalization/moving_mean": rng.randn(16).astype(np.float32),
+            "net/blocks_0/conv2d/kernel/Adam_1": rng.rand(3, 3, 8, 16).astype(np.float32),
+            "beta2_power": np.float32(0.99), "adam_step": np.int64(12)}
+
+
+def test_dump_outputs_writes_every_variable_and_the_loss(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per variable ('/' -> '.'), float32 (integer scalars float64), plus the loss -- unsampled
+    while the whole fits under the cap."""
+    import numpy as np
+    b = _bench()
+    named = _named()
+    info = b.dump_outputs(_StubLearner(named), 0.625, str(tmp_path / "d"))
+    files = sorted(os.listdir(str(tmp_path / "d")))
+    assert files == sorted([k.replace("/", ".") + ".npy" for k in named] + ["loss.npy"])
+    assert info["arrays"] == len(files) and not info["sampled"]
+    for k, v in named.items():
+        got = np.load(str(tmp_path / "d" / (k.replace("/", ".") + ".npy")))
+        assert got.dtype == (np.float64 if k == "adam_step" else np.float32)
+        assert got.shape == np.shape(v) and np.array_equal(got, np.asarray(v, dtype=got.dtype))
+    loss = np.load(str(tmp_path / "d" / "loss.npy"))
+    assert loss.dtype == np.float32 and loss.tolist() == [0.625]
+    assert info["bytes"] == sum(np.load(str(tmp_path / "d" / f)).nbytes for f in files)
+
+
+def test_dump_outputs_samples_the_same_elements_under_the_cap(tmp_path):
+    """Above the byte cap every array keeps the same seeded sample of its elements: never more than the cap, and the same indices in
+    two dumps of different values (so two builds compare element for element)."""
+    import numpy as np
+    b = _bench()
+    cap = 2000
+    a = b.dump_outputs(_StubLearner(_named(0)), 1.0, str(tmp_path / "a"), max_bytes=cap)
+    c = b.dump_outputs(_StubLearner(_named(1)), 2.0, str(tmp_path / "c"), max_bytes=cap)
+    assert a["sampled"] and c["sampled"] and a["bytes"] <= cap and a["bytes"] == c["bytes"]
+    k = "net.blocks_0.conv2d.kernel.npy"
+    ka, kc = np.load(str(tmp_path / "a" / k)), np.load(str(tmp_path / "c" / k))
+    full_a, full_c = _named(0)["net/blocks_0/conv2d/kernel"].reshape(-1), _named(1)["net/blocks_0/conv2d/kernel"].reshape(-1)
+    ia = [int(np.flatnonzero(full_a == x)[0]) for x in ka]
+    ic = [int(np.flatnonzero(full_c == x)[0]) for x in kc]
+    assert 0 < len(ia) < full_a.size and ia == ic == sorted(ia)
+    assert np.load(str(tmp_path / "a" / "adam_step.npy")).tolist() == 12.0     # (a scalar stays whole)
