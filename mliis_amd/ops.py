@@ -51,6 +51,49 @@ def _chk(t: torch.Tensor, dtype=torch.float32):
 DT_F32, DT_BF16 = 0, 1   # MLIIS_DT_* of include/mliis_hip.h: storage type of the expanded MBConv tensors (z0, z1, a1 and their gradients)
 
 
+def _dense(*tensors):
+    """Operands a kernel reads or writes as dense arrays (no leading dimension is passed): a channel-slice view or a transposed
+    tensor would be read as if it were packed -- refuse it.  Returns the first tensor (None passes)."""
+    for t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise MliisError("this entry point takes a dense tensor; got shape {} strides {} (a view with a row stride is only accepted "
+                             "where the wrapper passes a leading dimension)".format(tuple(t.shape), t.stride()))
+    return tensors[0] if tensors else None
+
+
+def _numel(shape) -> int:
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n
+
+
+def _out_dense(out, shape, dtype=torch.float32, what="out"):
+    """A caller-provided dense output: dtype, contiguity and element count of `shape` (leading dims may be folded)."""
+    if out is None:
+        return None
+    if dtype is not None and out.dtype != dtype:
+        raise MliisError("{}: expected {} tensor, got {}".format(what, dtype, out.dtype))
+    _dense(out)
+    if out.numel() != _numel(shape) or (out.dim() == len(shape) and tuple(out.shape) != tuple(shape)) or \
+            (out.dim() and len(shape) and out.shape[-1] != shape[-1]):
+        raise MliisError("{}: expected shape {}, got {}".format(what, tuple(shape), tuple(out.shape)))
+    return out
+
+
+def _out_rows(out, shape, dtype=torch.float32, what="out"):
+    """A caller-provided output the kernel writes through a leading dimension: dtype, uniform row stride, rows x channels of `shape`
+    and, when out keeps the full rank, the same outer dims."""
+    if out is None:
+        return None
+    if dtype is not None and out.dtype != dtype:
+        raise MliisError("{}: expected {} tensor, got {}".format(what, dtype, out.dtype))
+    rows, c, _ = rows_ld(out)
+    if c != shape[-1] or rows != _numel(shape[:-1]) or (out.dim() == len(shape) and tuple(out.shape) != tuple(shape)):
+        raise MliisError("{}: expected shape {}, got {}".format(what, tuple(shape), tuple(out.shape)))
+    return out
+
+
 def _dt(*tensors) -> int:
     """Storage-type code of tensors that must share it: float32 -> MLIIS_DT_F32, bfloat16 -> MLIIS_DT_BF16."""
     d = tensors[0].dtype
@@ -159,6 +202,8 @@ def stem_conv_fwd(x, w, idx=None, out=None, stats_part=None, rows=None):
     N = S if idx is None else idx.numel()
     Co = w.shape[-1]
     Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    _dense(x, w, idx, stats_part)
+    _out_dense(out, (N, Ho, Wo, Co), what="stem_conv_fwd out")
     out = torch.empty((N, Ho, Wo, Co), dtype=torch.float32, device=x.device) if out is None else out
     if stats_part is not None or rows:
         nblk = C.c_int(0)
@@ -185,6 +230,8 @@ def stem_conv_fwd_stats_floats(N, H, W, Co):
 def stem_conv_bwd_filter(x, dz, idx=None, out=None, ws: Optional[Workspace] = None, partial=None):
     S, H, W, _ = x.shape
     N, _, _, Co = dz.shape
+    _dense(x, idx, dz, partial)
+    _out_dense(out, (3, 3, 3, Co), what="stem_conv_bwd_filter out")
     if partial is not None:
         lib.call("mliis_stem_conv_bwd_filter", _ptr(x), _ptr(idx), _ptr(dz), None, N, H, W, Co, _MEAN3, _STD3, _ptr(partial), partial.numel(),
                  _stream())
@@ -204,6 +251,8 @@ def dwconv_fwd(x, w, stride, out=None, stats_part=None):
     N, H, W, C_ = x.shape
     k = w.shape[0]
     Ho, Wo = -(-H // stride), -(-W // stride)
+    _dense(x, w, stats_part)
+    _out_dense(out, (N, Ho, Wo, C_), what="dwconv_fwd out")
     out = torch.empty((N, Ho, Wo, C_), dtype=torch.float32, device=x.device) if out is None else out
     meta = dict(bytes=4.0 * (x.numel() + out.numel() + k * k * C_), shape=(N, H, W, C_, k, stride)) if PROFILE is not None else {}
     nblk = C.c_int(0)
@@ -221,6 +270,8 @@ def dwconv_bwd_data(dy, w, stride, in_hw, out=None, bn=None, part=None):
     N, _, _, C_ = dy.shape
     H, W = in_hw
     k = w.shape[0]
+    _dense(dy, w, part, *(bn or ()))
+    _out_dense(out, (N, H, W, C_), what="dwconv_bwd_data out")
     out = torch.empty((N, H, W, C_), dtype=torch.float32, device=dy.device) if out is None else out
     if bn is not None:
         z, mean, rstd, gamma, beta = bn
@@ -237,6 +288,8 @@ def dwconv_bwd_data(dy, w, stride, in_hw, out=None, bn=None, part=None):
 
 def dwconv_bwd_filter(x, dy, k, stride, out=None, ws: Optional[Workspace] = None, partial=None):
     N, H, W, C_ = x.shape
+    _dense(x, dy, partial)
+    _out_dense(out, (k, k, C_, 1), what="dwconv_bwd_filter out")
     if partial is not None:
         lib.call("mliis_dwconv_bwd_filter", _ptr(x), _ptr(dy), None, N, H, W, C_, k, stride, _ptr(partial), partial.numel(), _stream())
         return None
@@ -258,6 +311,8 @@ def dwconv_bn_fwd(z, w, stride, bn=None, part=None, nblk=0, out=None, stats_part
     N, H, W, C_ = z.shape
     k = w.shape[0]
     Ho, Wo = -(-H // stride), -(-W // stride)
+    _dense(z, w, part, stats_part, *(bn or ()))
+    _out_dense(out, (N, Ho, Wo, C_), None, what="dwconv_bn_fwd out")
     out = torch.empty((N, Ho, Wo, C_), dtype=z.dtype, device=z.device) if out is None else out
     g, b, m, r, mm, mv = bn if bn is not None else (None,) * 6
     meta = dict(bytes=float(z.numel() * z.element_size() + out.numel() * out.element_size() + 4 * k * k * C_),
@@ -282,6 +337,9 @@ def dwconv_bn_bwd(dy, z, w, stride, bn=None, out=None, dw=None, dw_part=None, bn
     the given dw) and, with bn_part, stage 1 of the batch norm's backward [blocks][2][C].  Returns (dx, dw | None, blocks)."""
     N, H, W, C_ = z.shape
     k = w.shape[0]
+    _dense(dy, z, w, dw_part, bn_part, *(bn or ()))
+    _out_dense(out, (N, H, W, C_), None, what="dwconv_bn_bwd out")
+    _out_dense(dw, (k, k, C_, 1), what="dwconv_bn_bwd dw")
     out = torch.empty((N, H, W, C_), dtype=z.dtype, device=z.device) if out is None else out
     blocks = dwconv_bn_bwd_blocks(N, H, W, C_, k, stride)
     if dw_part is None:
@@ -302,6 +360,8 @@ def mbconv_dw_bwd_march(da2, z1, bn1, gate, chan_add, stage1, dgamma1, dbeta1, z
     beta); stage1 [N][2][C] from se_mlp_bwd_bn.  Returns the block count (slabs of dw_part, blocks of bn_part)."""
     N, H, W, C_ = z0.shape
     k = w.shape[0]
+    _dense(da2, z1, gate, chan_add, stage1, z0, w, dw_part, bn_part, *bn1, *bn0)
+    _out_dense(out, (N, H, W, C_), None, what="mbconv_dw_bwd_march out")
     nb = C.c_int(0)
     meta = dict(bytes=4.0 * (2 * z0.numel() + 2 * z1.numel() + 2 * k * k * C_), shape=(N, H, W, C_, k, stride)) if PROFILE is not None else {}
     _timed("dwconv_bn_bwd", meta, lambda: lib.call(
@@ -340,6 +400,7 @@ def mbconv_dw_fwd_small(z0, part0, nblk0, bn0, w, bn1, z1, a1, s, a0=None, eps=B
     k = w.shape[0]
     g0, b0, m0, r0, mm0, mv0 = bn0
     g1, b1, m1, r1, mm1, mv1 = bn1
+    _dense(z0, part0, w, a0, z1, a1, s, z0_blocked, *bn0, *bn1)
     lib.call("mliis_mbconv_dw_fwd_small", _aptr(z0), _ptr(part0), int(nblk0), _ptr(g0), _ptr(b0), _ptr(m0), _ptr(r0), _ptr(mm0), _ptr(mv0),
              _ptr(w), _ptr(g1), _ptr(b1), _ptr(m1), _ptr(r1), _ptr(mm1), _ptr(mv1), _aptr(a0), _aptr(z1), _aptr(a1), _ptr(s), N, H, W, C_, k,
              float(eps), float(momentum), int(group_width), _dt(z0, z1, a1) if a0 is None else _dt(z0, z1, a1, a0),
@@ -354,6 +415,7 @@ def mbconv_dw_bwd_small(da2, gate, chan_add, z1, bn1, w, z0, bn0, dgamma1, dbeta
     (conv2d_bwd_data(gate=..., out_block=group width))."""
     N, H, W, C_ = z1.shape
     k = w.shape[0]
+    _dense(da2, gate, chan_add, z1, w, z0, dw, dz0, z0_blocked, *bn1, *bn0)
     lib.call("mliis_mbconv_dw_bwd_small", _aptr(da2), _ptr(gate), _ptr(chan_add), _aptr(z1), _ptr(bn1[0]), _ptr(bn1[1]), _ptr(bn1[2]),
              _ptr(bn1[3]), _ptr(w), _aptr(z0), _ptr(bn0[0]), _ptr(bn0[1]), _ptr(bn0[2]), _ptr(bn0[3]), _ptr(dgamma1), _ptr(dbeta1), _ptr(dw),
              _ptr(dgamma0), _ptr(dbeta0), _aptr(dz0), N, H, W, C_, k, int(group_width), _dt(da2, z1, z0, dz0),
@@ -372,6 +434,7 @@ def transpose_weights(src, dst, desc, amax=None, tiles=0, x3=None, rng=None):
     float [n]): also max |w| per tensor -- the fp8 operand scale.  tiles = transpose_tiles(rows of desc): one workgroup per 32 x 32
     tile; 0: a fixed grid that strides over the tiles.  x3 (an X3Images over the same arena): its images are rebuilt too.
     rng = (generator state, MaskPlan): the masks of the training step are drawn by the same launch (rng_masks)."""
+    _dense(src, dst, desc, amax)
     if rng is not None and tiles > 0:
         st, plan = rng
         has = x3 is not None and x3.desc is not None
@@ -408,10 +471,13 @@ def conv2d_fwd(x, w, bias=None, dil=1, out=None, accumulate=False, ws: Optional[
     group-blocked layout [Cout / v][N H W][v] (streamed 1x1 plan only: conv1x1_stream_eligible)."""
     N, H, W = nhw if nhw is not None else x.shape[:3]
     k, _, Cin_total, Cout = w.shape
-    wt = hwoi(w) if wt is None else wt
     rows, Cin, ldx = rows_ld(x)
     if ci_begin + Cin > Cin_total:
         raise MliisError("conv2d_fwd: x has {} channels, weight has {} (window starts at {})".format(Cin, Cin_total, ci_begin))
+    _dense(wt, bias, x_scale, border_bias, stats_part, fp8_w_amax)
+    if not out_block:
+        _out_rows(out, (N, H, W, Cout), None, what="conv2d_fwd out")
+    wt = hwoi(w) if wt is None else wt
     out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x.device) if out is None else out
     _, co, ldy = rows_ld(out)
     ws = ws or default_ws()
@@ -453,6 +519,10 @@ def conv2d_fwd_bnin(z, part, nblk, mean, rstd, gamma, beta, a_out, w, out, movin
     k, _, Cin_w, Cout = w.shape
     if k != 1 or Cin_w != Cin:
         raise MliisError("conv2d_fwd_bnin: a 1x1 weight over the {} channels of z expected, got {}".format(Cin, tuple(w.shape)))
+    _dense(wt, part, mean, rstd, gamma, beta, img_scale, stats_part, *(moving or ()))
+    if not out_block:
+        _out_rows(out, (N, H, W, Cout), None, what="conv2d_fwd_bnin out")
+    _out_rows(a_out, (N, H, W, Cin), what="conv2d_fwd_bnin a_out")
     wt = hwoi(w) if wt is None else wt
     _, _, ldy = rows_ld(out)
     _, _, ldo = rows_ld(a_out)
@@ -541,6 +611,8 @@ def conv2d_fwd_x3(x, image, k, cout, bias=None, dil=1, out=None, accumulate=Fals
     -- the window is the one the image was packed for.  Returns out, or (out, nblk) with stats_part."""
     N, H, W = x.shape[:3]
     rows, Cin, ldx = rows_ld(x)
+    _dense(image, bias, border_bias, stats_part)
+    _out_rows(out, (N, H, W, cout), what="conv2d_fwd_x3 out")
     out = torch.empty((N, H, W, cout), dtype=torch.float32, device=x.device) if out is None else out
     _, co, ldy = rows_ld(out)
     ws = ws or default_ws()
@@ -561,6 +633,8 @@ def conv2d_bwd_data_x3(dy, image, k, cin_out, dil=1, out=None, accumulate=False,
     """conv2d_bwd_data under MLIIS_PREC_F32X3 with the conv's backward weight image (its input-channel window has cin_out channels)."""
     N, H, W = dy.shape[:3]
     rows, Cout, lddy = rows_ld(dy)
+    _dense(image)
+    _out_rows(out, (N, H, W, cin_out), what="conv2d_bwd_data_x3 out")
     out = torch.empty((N, H, W, cin_out), dtype=torch.float32, device=dy.device) if out is None else out
     _, ci, lddx = rows_ld(out)
     ws = ws or default_ws()
@@ -590,6 +664,9 @@ def conv2d_bwd_data(dy, w, dil=1, ci_begin=0, ci_count=None, out=None, accumulat
     _, cy, lddy = rows_ld(dy)
     if cy != Cout:
         raise MliisError("conv2d_bwd_data: dy has {} channels, weight has {}".format(cy, Cout))
+    _dense(w, part, *((bn[1], bn[2], bn[3]) if bn is not None else ()))
+    if not out_block:
+        _out_rows(out, (N, H, W, ci_count), None, what="conv2d_bwd_data out")
     out = torch.empty((N, H, W, ci_count), dtype=torch.float32, device=dy.device) if out is None else out
     _, _, lddx = rows_ld(out)
     ws = ws or default_ws()
@@ -630,6 +707,12 @@ def conv2d_bwd_filter(x, dy, k, dil=1, out=None, accumulate=False, ws: Optional[
     _, Cin, ldx = rows_ld(x)
     _, Cout, lddy = rows_ld(dy)
     prec = _prec(precision)
+    _dense(x_scale, partial)
+    if out is not None:
+        _dense(out)
+        if out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[:2]) != (k, k) or out.shape[3] != Cout or ci_begin + Cin > out.shape[2]:
+            raise MliisError("conv2d_bwd_filter out: expected [{k},{k},>={c},{o}] float32, got {s} {d}".format(
+                k=k, c=ci_begin + Cin, o=Cout, s=tuple(out.shape), d=out.dtype))
     if partial is not None:
         lib.call("mliis_conv2d_bwd_filter", _ptr(x), ldx, _ptr(x_scale), _ptr(dy), lddy, None, N, H, W, Cin, 0, Cin, Cout, k, dil, 0,
                  _ptr(partial), partial.numel(), prec, _stream())
@@ -660,6 +743,7 @@ class FilterBatch:
         N, H, W = dy.shape[:3]
         _, Cin, ldx = rows_ld(x)
         _, Cout, lddy = rows_ld(dy)
+        _dense(partial, x_scale)
         plan = (C.c_int * 8)()
         lib.call("mliis_conv2d_bwd_filter_plan", N, H, W, Cin, Cout, k, plan)
         tmf, nt, multitap, gx, gy, gz, rps = [int(v) for v in plan[:7]]
@@ -753,6 +837,8 @@ def rsd_concat_pool(deep, skip, cat, pool_part):
     N, H, W = cat.shape[:3]
     _, Cd, ldd = rows_ld(deep)
     _, Cs, lds = rows_ld(skip)
+    _dense(pool_part)
+    _out_rows(cat, (N, H, W, Cd + Cs), what="rsd_concat_pool cat")
     ch = C.c_int(0)
     lib.call("mliis_rsd_concat_pool", _ptr(_chk(deep)), ldd, deep.shape[1], deep.shape[2], Cd, _ptr(_chk(skip)), lds, Cs, _ptr(cat), rows_ld(cat)[2],
              N, H, W, _ptr(pool_part), pool_part.numel(), C.byref(ch), _stream())
@@ -768,6 +854,8 @@ def rsd_pool_fwd(pool, w, c_begin, out=None, chunks=1, scale=1.0, pool_out=None)
     (chunks > 1) the chunk partials [N, chunks, Cp] of rsd_concat_pool with their scale; pool_out [N, Cp] keeps the folded vectors."""
     N, Cp = (pool.shape[0], pool.shape[-1]) if pool_out is None else pool_out.shape   # (the partials may arrive as a flat buffer)
     _, _, Cin_total, Co = w.shape
+    _dense(pool, w, pool_out)
+    _out_dense(out, (N, 9, Co), what="rsd_pool_fwd out")
     out = torch.empty((N, 9, Co), dtype=torch.float32, device=pool.device) if out is None else out
     lib.call("mliis_rsd_pool_fwd", _ptr(pool), int(chunks), float(scale), _ptr(pool_out), _ptr(w), _ptr(out), N, Cp, Cin_total, c_begin, Co, _stream())
     return out
@@ -779,6 +867,8 @@ def rsd_pool_bwd(dz, tot, pool, w, c_begin, dw, dbias=None, dpool=None, ws: Opti
     _, Co, lddz = rows_ld(dz)
     Cp = pool.shape[1]
     Cin_total = w.shape[2]
+    _dense(tot, pool, w, dw, dbias)
+    _out_dense(dpool, (N, Cp), what="rsd_pool_bwd dpool")
     dpool = torch.empty((N, Cp), dtype=torch.float32, device=dz.device) if dpool is None else dpool
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_rsd_pool_bwd_workspace_floats", N, Co))
@@ -791,6 +881,9 @@ def rsd_pool_bwd(dz, tot, pool, w, c_begin, dw, dbias=None, dpool=None, ws: Opti
 def bn_stats(x, pre_swish=False, moving=None, unbiased_moving_var=False, mean=None, rstd=None, eps=BN_EPS, momentum=BN_MOMENTUM,
              ws: Optional[Workspace] = None):
     rows, C_, ldx = rows_ld(x)
+    _out_dense(mean, (C_,), what="bn_stats mean")
+    _out_dense(rstd, (C_,), what="bn_stats rstd")
+    _dense(*(moving or ()))
     mean = torch.empty(C_, dtype=torch.float32, device=x.device) if mean is None else mean
     rstd = torch.empty(C_, dtype=torch.float32, device=x.device) if rstd is None else rstd
     ws = ws or default_ws()
@@ -804,6 +897,7 @@ def bn_stats(x, pre_swish=False, moving=None, unbiased_moving_var=False, mean=No
 def bn_stats_partial(x, pre_swish, part):
     """Stage-1 statistics of x into `part` ([nblk][2][C]); returns nblk."""
     rows, C_, ldx = rows_ld(x)
+    _dense(part)
     nblk = C.c_int(0)
     lib.call("mliis_bn_stats_partial", _ptr(x), ldx, rows, C_, int(pre_swish), _ptr(part), part.numel(), C.byref(nblk), _stream())
     return nblk.value
@@ -818,6 +912,8 @@ def bn_apply_fused(x, part, nblk, mean, rstd, gamma, beta, moving=None, unbiased
     """pool_part (a float buffer): the pass also leaves per-image partial sums of its output there and the function returns
     (out, chunks_per_image) -- feed both to se_mlp_fwd."""
     rows, C_, ldx = rows_ld(x)
+    _dense(part, mean, rstd, gamma, beta, img_scale, pool_part, *(moving or ()))
+    _out_rows(out, tuple(x.shape), None, what="bn_apply_fused out")
     out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
     _, _, ldy = rows_ld(out)
     rpi = rows_per_img or (rows // x.shape[0])
@@ -835,6 +931,8 @@ def bn_apply_fused(x, part, nblk, mean, rstd, gamma, beta, moving=None, unbiased
 
 def bn_apply(x, mean, rstd, gamma, beta, pre_swish=False, post_swish=False, img_scale=None, res=None, out=None, rows_per_img=None):
     rows, C_, ldx = rows_ld(x)
+    _dense(mean, rstd, gamma, beta, img_scale)
+    _out_rows(out, tuple(x.shape), what="bn_apply out")
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
     _, _, ldy = rows_ld(out)
     rpi = rows_per_img or (rows // x.shape[0])
@@ -851,6 +949,10 @@ def bn_bwd(x, dy, mean, rstd, gamma, beta, pre_swish=False, post_swish=False, im
     dxsum_part (optional, bn_bwd_dxsum_floats(rows, C) floats): per-row-chunk column sums of dx (slabs for fold_batched)."""
     rows, C_, ldx = rows_ld(x)
     _, _, lddy = rows_ld(dy)
+    _dense(mean, rstd, gamma, beta, img_scale, chan_scale, chan_add, dxsum_part, stage1[0] if stage1 else None)
+    _out_rows(dx, tuple(x.shape), None, what="bn_bwd dx")
+    _out_dense(dgamma, (C_,), what="bn_bwd dgamma")
+    _out_dense(dbeta, (C_,), what="bn_bwd dbeta")
     dx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if dx is None else dx
     _, _, lddx = rows_ld(dx)
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device) if dgamma is None else dgamma
@@ -876,6 +978,7 @@ def bn_apply_fused_pair(probs, pre_swish=False, post_swish=False, unbiased_movin
         raise MliisError("bn_apply_fused_pair: the two problems must have the same shape and leading dimensions")
     mm0, mw0 = mv0 if mv0 is not None else (None, None)
     mm1, mw1 = mv1 if mv1 is not None else (None, None)
+    _dense(pt0, m0, r0, g0, b0, mm0, mw0, pt1, m1, r1, g1, b1, mm1, mw1)
     lib.call("mliis_bn_apply_fused_pair", _ptr(_chk(x0)), _ptr(y0), _ptr(pt0), int(nb0), _ptr(m0), _ptr(r0), _ptr(mm0), _ptr(mw0), _ptr(g0), _ptr(b0),
              _ptr(_chk(x1)), _ptr(y1), _ptr(pt1), int(nb1), _ptr(m1), _ptr(r1), _ptr(mm1), _ptr(mw1), _ptr(g1), _ptr(b1), ldx, ldy, rows, C_,
              float(eps), float(momentum), int(unbiased_moving_var), int(pre_swish), int(post_swish), _stream())
@@ -891,6 +994,7 @@ def bn_bwd_pair(probs, pre_swish=False, post_swish=False, ws: Optional[Workspace
     _, _, lddx = rows_ld(dx0)
     if rows_ld(x1) != (rows, C_, ldx) or rows_ld(dy1) != (rows, C_, lddy) or rows_ld(dx1) != (rows, C_, lddx):
         raise MliisError("bn_bwd_pair: the two problems must have the same shape and leading dimensions")
+    _dense(m0, r0, g0, b0, dg0, db0, ds0, m1, r1, g1, b1, dg1, db1, ds1)
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_colreduce_workspace_floats", rows, C_, 2, 2))
     lib.call("mliis_bn_bwd_pair", _ptr(_chk(x0)), _ptr(dy0), _ptr(dx0), _ptr(m0), _ptr(r0), _ptr(g0), _ptr(b0), _ptr(dg0), _ptr(db0), _ptr(ds0),
@@ -906,6 +1010,7 @@ def bn_bwd_dxsum_floats(rows, C_):
 def colsum(a, b=None, nseg=1, scale=1.0, out=None, accumulate=False, ws: Optional[Workspace] = None):
     rows, C_, lda = rows_ld(a)
     ldb = rows_ld(b)[2] if b is not None else 0
+    _out_dense(out, (nseg, C_), what="colsum out")
     out = torch.empty((nseg, C_), dtype=torch.float32, device=a.device) if out is None else out
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_colreduce_workspace_floats", rows // nseg, C_, nseg, 1))
@@ -922,6 +1027,9 @@ def se_mlp_fwd(s, w1, b1, w2, b2, hpre=None, gate=None, chunks=0, scale=1.0, s_o
         raise MliisError("se_mlp_fwd: partial sums need an s_out [N, C] tensor")
     N, C_ = s.shape if chunks == 0 else s_out.shape
     R = b1.numel()
+    _dense(s, s_out, w1, b1, w2, b2)
+    _out_dense(hpre, (N, R), what="se_mlp_fwd hpre")
+    _out_dense(gate, (N, C_), what="se_mlp_fwd gate")
     hpre = torch.empty((N, R), dtype=torch.float32, device=s.device) if hpre is None else hpre
     gate = torch.empty((N, C_), dtype=torch.float32, device=s.device) if gate is None else gate
     lib.call("mliis_se_mlp_fwd", _ptr(s), max(1, int(chunks)), float(scale), _ptr(s_out), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(hpre),
@@ -931,6 +1039,7 @@ def se_mlp_fwd(s, w1, b1, w2, b2, hpre=None, gate=None, chunks=0, scale=1.0, s_o
 
 def se_wgrad_batched(desc, total_tiles):
     """Deferred squeeze-excite weight gradients of every block in one launch (desc: device int64 [n,12], include/mliis_hip.h)."""
+    _dense(desc)
     lib.call("mliis_se_wgrad_batched", _ptr(desc), int(desc.shape[0]), int(total_tiles), _stream())
 
 
@@ -945,6 +1054,7 @@ def se_mlp_bwd(dgate, gate, s, hpre, w1, w2, hw, outs=None, dgate_groups=0, w1t=
         outs = dict(dpre1=torch.empty((N, R), device=dev), dpre2=torch.empty((N, C_), device=dev), chan_add=torch.empty((N, C_), device=dev),
                     dw1=torch.empty((1, 1, C_, R), device=dev), db1=torch.empty(R, device=dev), dw2=torch.empty((1, 1, R, C_), device=dev),
                     db2=torch.empty(C_, device=dev))
+    _dense(dgate, gate, s, hpre, w1, w2, w1t, *outs.values())
     lib.call("mliis_se_mlp_bwd", _ptr(dgate), int(dgate_groups), _ptr(gate), _ptr(s), _ptr(hpre), _ptr(w1), _ptr(w1t), _ptr(w2), _ptr(outs["dpre1"]),
              _ptr(outs["dpre2"]), _ptr(outs["chan_add"]), _ptr(outs.get("dw1")), _ptr(outs.get("db1")), _ptr(outs.get("dw2")), _ptr(outs.get("db2")), N, C_, R, hw,
              _stream())
@@ -957,6 +1067,7 @@ def se_bn_bwd_sums(z1, da2, mean, rstd, gamma, beta, part):
     N = z1.shape[0]
     rows, C_, ldx = rows_ld(z1)
     _, _, ldd = rows_ld(da2)
+    _dense(mean, rstd, gamma, beta, part)
     nb = C.c_int(0)
     lib.call("mliis_se_bn_bwd_sums", _aptr(z1), ldx, _aptr(da2), ldd, N, rows // N, C_, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
              _ptr(part), part.numel(), C.byref(nb), _dt(z1, da2), _stream())
@@ -972,6 +1083,7 @@ def se_mlp_bwd_bn(sums, nblk, gate, hpre, w1, w2, hw, outs, stage1, w1t=None):
     (stage1, N) to bn_bwd(stage1=...) together with chan_scale = gate and chan_add)."""
     N, C_ = gate.shape
     R = hpre.shape[1]
+    _dense(sums, gate, hpre, w1, w1t, w2, stage1, *outs.values())
     lib.call("mliis_se_mlp_bwd_bn", _ptr(sums), int(nblk), _ptr(gate), _ptr(hpre), _ptr(w1), _ptr(w1t), _ptr(w2), _ptr(outs["dpre1"]),
              _ptr(outs["dpre2"]), _ptr(outs["chan_add"]), _ptr(stage1), N, C_, R, hw, _stream())
     return outs
@@ -981,6 +1093,8 @@ def chan_affine(x, S=None, A=None, out=None, accumulate=False, rows_per_img=None
     ref = x if x is not None else (out if out is not None else like)
     rows, C_, _ = rows_ld(ref)
     ldx = rows_ld(x)[2] if x is not None else 0
+    _dense(S, A)
+    _out_rows(out, tuple(ref.shape), what="chan_affine out")
     out = torch.empty(ref.shape, dtype=torch.float32, device=ref.device) if out is None else out
     _, _, ldy = rows_ld(out)
     rpi = rows_per_img or (rows // ref.shape[0])
@@ -992,6 +1106,9 @@ def chan_split(x, c0, out0, acc0, out1, acc1, A=None, rows_per_img=None):
     """out0 (+)= x[..., :c0] + A[n, :c0];  out1 (+)= x[..., c0:] + A[n, c0:]   (one pass; channel-slice views allowed)"""
     rows, C_, ldx = rows_ld(x)
     rpi = rows_per_img or (rows // x.shape[0])
+    _dense(A)
+    _out_rows(out0, tuple(x.shape[:-1]) + (int(c0),), what="chan_split out0")
+    _out_rows(out1, tuple(x.shape[:-1]) + (C_ - int(c0),), what="chan_split out1")
     lib.call("mliis_chan_split", _ptr(x), ldx, _ptr(A), _ptr(out0), rows_ld(out0)[2], int(c0), int(acc0), _ptr(out1), rows_ld(out1)[2], int(acc1),
              rows, C_, rpi, _stream())
 
@@ -999,6 +1116,7 @@ def chan_split(x, c0, out0, acc0, out1, acc1, A=None, rows_per_img=None):
 def swish_mask_fwd(z, mask=None, out=None, pre_mask=False):
     """ASPP activation: out = swish(z) * mask, or swish(z * mask) with pre_mask (mask None = inference).  Channel-slice views allowed."""
     rows, C_, ldz = rows_ld(z)
+    _out_rows(out, tuple(z.shape), what="swish_mask_fwd out")
     out = torch.empty(z.shape, dtype=torch.float32, device=z.device) if out is None else out
     ldm = rows_ld(mask)[2] if mask is not None else 0
     lib.call("mliis_swish_mask_fwd", _ptr(z), ldz, _ptr(mask), ldm, _ptr(out), rows_ld(out)[2], rows, C_, int(pre_mask), _stream())
@@ -1007,6 +1125,7 @@ def swish_mask_fwd(z, mask=None, out=None, pre_mask=False):
 
 def swish_mask_bwd(dy, z, mask=None, out=None, pre_mask=False):
     rows, C_, lddy = rows_ld(dy)
+    _out_rows(out, tuple(z.shape), what="swish_mask_bwd out")
     out = torch.empty(z.shape, dtype=torch.float32, device=z.device) if out is None else out
     ldm = rows_ld(mask)[2] if mask is not None else 0
     lib.call("mliis_swish_mask_bwd", _ptr(dy), lddy, _ptr(z), rows_ld(z)[2], _ptr(mask), ldm, _ptr(out), rows_ld(out)[2], rows, C_,
@@ -1019,6 +1138,7 @@ def resize_bilinear_fwd(x, out_hw, out=None):
     N, Hi, Wi = x.shape[:3]
     _, C_, ldx = rows_ld(x)
     Ho, Wo = out_hw
+    _out_rows(out, (N, Ho, Wo, C_), what="resize_bilinear_fwd out")
     out = torch.empty((N, Ho, Wo, C_), dtype=torch.float32, device=x.device) if out is None else out
     _, _, ldy = rows_ld(out)
     lib.call("mliis_resize_bilinear_fwd", _ptr(x), ldx, _ptr(out), ldy, N, Hi, Wi, Ho, Wo, C_, _stream())
@@ -1029,6 +1149,7 @@ def resize_bilinear_bwd(dy, in_hw, out=None, accumulate=False):
     N, Ho, Wo = dy.shape[:3]
     _, C_, lddy = rows_ld(dy)
     Hi, Wi = in_hw
+    _out_rows(out, (N, Hi, Wi, C_), what="resize_bilinear_bwd out")
     out = torch.empty((N, Hi, Wi, C_), dtype=torch.float32, device=dy.device) if out is None else out
     _, _, lddx = rows_ld(out)
     lib.call("mliis_resize_bilinear_bwd", _ptr(dy), lddy, _ptr(out), lddx, N, Hi, Wi, Ho, Wo, C_, int(accumulate), _stream())
@@ -1037,6 +1158,10 @@ def resize_bilinear_bwd(dy, in_hw, out=None, accumulate=False):
 
 def final_conv_fwd(x, w, b, mask=None, out=None):
     rows, C_, ldx = rows_ld(x)
+    _dense(w, b, mask)
+    if mask is not None and mask.numel() != rows * C_:
+        raise MliisError("final_conv_fwd: mask must be a dense [rows, {}] tensor, got {}".format(C_, tuple(mask.shape)))
+    _out_dense(out, tuple(x.shape[:-1]) + (2,), what="final_conv_fwd out")
     out = torch.empty(tuple(x.shape[:-1]) + (2,), dtype=torch.float32, device=x.device) if out is None else out
     lib.call("mliis_final_conv_fwd", _ptr(x), ldx, _ptr(mask), _ptr(w), _ptr(b), _ptr(out), rows, C_, _stream())
     return out
@@ -1045,6 +1170,10 @@ def final_conv_fwd(x, w, b, mask=None, out=None):
 def final_conv_bwd_data(dy, w, C_, mask=None, out=None, fin=None):
     """fin = (partials buffer of head_ce_fused(finalize=False), image size (H, W), extra_loss, loss_out): the loss fold rides in this launch."""
     rows = dy.numel() // 2
+    _dense(dy, w, mask)
+    if mask is not None and mask.numel() != rows * C_:
+        raise MliisError("final_conv_bwd_data: mask must be a dense [rows, {}] tensor, got {}".format(C_, tuple(mask.shape)))
+    _out_rows(out, tuple(dy.shape[:-1]) + (C_,), what="final_conv_bwd_data out")
     out = torch.empty(tuple(dy.shape[:-1]) + (C_,), dtype=torch.float32, device=dy.device) if out is None else out
     _, _, lddx = rows_ld(out)
     if fin is not None:
@@ -1059,6 +1188,11 @@ def final_conv_bwd_data(dy, w, C_, mask=None, out=None, fin=None):
 
 def final_conv_bwd_filter(x, dy, mask=None, dw=None, db=None, ws: Optional[Workspace] = None):
     rows, C_, ldx = rows_ld(x)
+    _dense(dy, mask)
+    if mask is not None and mask.numel() != rows * C_:
+        raise MliisError("final_conv_bwd_filter: mask must be a dense [rows, {}] tensor, got {}".format(C_, tuple(mask.shape)))
+    _out_dense(dw, (1, 1, C_, 2), what="final_conv_bwd_filter dw")
+    _out_dense(db, (2,), what="final_conv_bwd_filter db")
     dw = torch.empty((1, 1, C_, 2), dtype=torch.float32, device=x.device) if dw is None else dw
     db = torch.empty(2, dtype=torch.float32, device=x.device) if db is None else db
     ws = ws or default_ws()
@@ -1071,6 +1205,9 @@ def softmax_ce(logits, labels, idx=None, label_smoothing=0.0, dice=False, extra_
                pred=None, out=None, ws: Optional[Workspace] = None):
     N, H, W, _ = logits.shape
     dev = logits.device
+    _dense(logits, labels, idx)
+    _out_dense(dlogits, tuple(logits.shape), what="softmax_ce dlogits")
+    _out_dense(pred, tuple(logits.shape), what="softmax_ce pred")
     if want_grad and dlogits is None:
         dlogits = torch.empty_like(logits)
     if want_pred and pred is None:
@@ -1088,6 +1225,8 @@ def head_ce_fused(small, labels, idx, size, label_smoothing, dsmall, out, extra_
     the full-resolution logits are never written (two launches instead of five).  finalize=False: ONE launch -- the loss partials stay
     in the workspace buffer (returned third; nothing else may use it meanwhile) for final_conv_bwd_data(fin=...) to fold."""
     N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx)
+    _out_dense(dsmall, tuple(small.shape), what="head_ce_fused dsmall")
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_head_ce_fused_workspace_floats", N, Hd, Wd))
     _timed("head_ce_fused", {}, lambda: lib.call("mliis_head_ce_fused", _ptr(_chk(small)), _ptr(labels), _ptr(idx), N, Hd, Wd, int(size[0]), int(size[1]),
@@ -1099,6 +1238,8 @@ def head_ce_fused(small, labels, idx, size, label_smoothing, dsmall, out, extra_
 def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None):
     """out[0] += weight * max_pos sum_n |logits[n, pos]|;  dlogits += its gradient (models/regularizers.py:20-22)."""
     N = logits.shape[0]
+    _dense(logits)
+    _out_dense(dlogits, tuple(logits.shape), what="darc1 dlogits")
     ws = ws or default_ws()
     buf = ws.get(2048)
     lib.call("mliis_darc1", _ptr(_chk(logits)), N, logits.numel() // N, float(weight), _ptr(dlogits), _ptr(out), _ptr(buf), buf.numel(), _stream())
@@ -1107,6 +1248,7 @@ def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None
 def fold_batched(part_base, out_base, desc, total_tiles, se_desc=None, se_tiles=0):
     """One launch folding every deferred weight-gradient slab set (desc: device int64 [n,8], see include/mliis_hip.h).  se_desc /
     se_tiles (the arguments of se_wgrad_batched): the squeeze-excite weight gradients ride in the same launch."""
+    _dense(part_base, out_base, desc, se_desc)
     lib.call("mliis_fold_batched", _ptr(part_base), _ptr(out_base), _ptr(desc), int(desc.shape[0]), int(total_tiles),
              _ptr(se_desc), int(se_desc.shape[0]) if se_desc is not None else 0, int(se_tiles) if se_desc is not None else 0, _stream())
 
@@ -1142,24 +1284,38 @@ def rng_masks(state: torch.Tensor, plan: MaskPlan):
 
 # ------------------------------------------------------------------------------------------------ optimizer / arena
 def sgd_fused(w, g, lr, l2_quad_mask=None, l2=0.0, lr_dev=None, l1=0.0):
+    _dense(w, g, l2_quad_mask)
+    _out_dense(g, tuple(w.shape), what="sgd_fused g")
     lib.call("mliis_sgd_fused", _ptr(w), _ptr(g), _ptr(l2_quad_mask), w.numel(), float(lr), _ptr(lr_dev), float(l2), float(l1), _stream())
 
 
 def adam_b1zero_fused(w, g, v, step_dev, lr, l2_quad_mask=None, l2=0.0, lr_dev=None, beta2=0.999, eps=1e-8, l1=0.0, ticket=None):
     """step_dev: device float, steps applied so far.  ticket None: the caller advanced it before the call; ticket (a zeroed device
     int32): the launch is step step_dev + 1 and advances the count itself (graph-replay safe)."""
+    _dense(w, g, v, l2_quad_mask)
+    _out_dense(g, tuple(w.shape), what="adam_b1zero_fused g")
+    _out_dense(v, tuple(w.shape), what="adam_b1zero_fused v")
     lib.call("mliis_adam_b1zero_fused", _ptr(w), _ptr(g), _ptr(v), _ptr(l2_quad_mask), w.numel(), float(lr), _ptr(lr_dev), float(l2), float(l1),
              float(beta2), float(eps), _ptr(step_dev), _ptr(ticket), _stream())
 
 
 def axpby(a, x, b, y):
+    _dense(x, y)
+    if x is not None:
+        _out_dense(x, tuple(y.shape), what="axpby x")
     lib.call("mliis_axpby", float(a), _ptr(x), float(b), _ptr(y), y.numel(), _stream())
 
 
 def copy_words(src, dst):
     """dst <- src (<= 1024 32-bit words) by one small kernel on the current stream; src may be a pinned HOST tensor."""
+    _dense(src, dst)
+    if dst.numel() < src.numel() or dst.element_size() != 4 or src.element_size() != 4:
+        raise MliisError("copy_words: dst must hold src's {} 32-bit words".format(src.numel()))
     lib.call("mliis_copy_words", C.c_void_p(src.data_ptr()), _ptr(dst), src.numel(), _stream())
 
 
 def lincomb(a, x, b, y, out):
+    _dense(x, y, out)
+    _out_dense(x, tuple(out.shape), what="lincomb x")
+    _out_dense(y, tuple(out.shape), what="lincomb y")
     lib.call("mliis_lincomb", float(a), _ptr(x), float(b), _ptr(y), _ptr(out), out.numel(), _stream())
