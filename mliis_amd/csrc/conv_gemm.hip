@@ -509,9 +509,6 @@ static inline bool ksplit_plan(long long M, int K, int Nout, int num_cus, Stream
 }
 static bool launch_ksplit(const StreamPlan& sp, const ConvGemmParams& p_, hipStream_t stream, int precision) {
   ConvGemmParams p = p_;
-#ifdef KS_DBG
-  p.dbg_stamps = getenv("MLIIS_KS_STAMPS") ? (unsigned long long*)strtoull(getenv("MLIIS_KS_STAMPS"), nullptr, 0) : nullptr;
-#endif
   dim3 grid(sp.gx, sp.gy);
   if (precision != MLIIS_PREC_FP32) return launch_ksplit_lowp(precision, sp.kc, sp.nt, grid, p, sp.row_groups, stream);
   return launch_ksplit_t<0>(sp.kc, sp.nt, grid, p, sp.row_groups, stream);

@@ -79,9 +79,6 @@ struct ConvGemmParams {
   const float* ain_scale = nullptr;   // nullable [Nimg]
   float* ain_out = nullptr;
   int ain_ldo = 0;
-#ifdef KS_DBG
-  unsigned long long* dbg_stamps = nullptr;   // [workgroups][8] wall-clock stamps (100 MHz) of thread 0
-#endif
 };
 
 __device__ __forceinline__ float4 buf_ld4_bf16(__amdgpu_buffer_rsrc_t r, unsigned byte_off);
@@ -1084,17 +1081,8 @@ __global__ __launch_bounds__(64 * kStreamWaves, 4) void conv1x1_stream_k(ConvGem
 // flight), the WV partial accumulators meet in LDS, and the first 64 NT threads finish the rows: sum in wave order (deterministic),
 // bias, accumulate, coalesced float4 stores, BN statistics.  One launch, no slabs, every load of a row group issued at once.
 // grid = (row-group blocks, column tiles); block = 64 WV threads.
-#ifdef KS_DBG
-#define KS_STAMP(k) do { ks_st[k] = wall_clock64(); } while (0)
-#else
-#define KS_STAMP(k) do { } while (0)
-#endif
 template <int KC, int NT, int WV, int PREC>
 __global__ __launch_bounds__(64 * WV, (KC <= 6 && KC * NT <= 8) ? 4 : 2) void conv1x1_ksplit_k(ConvGemmParams p, int row_groups) {   // (KC <= 6, KC NT <= 8: two workgroups per CU)
-#ifdef KS_DBG
-  unsigned long long ks_st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  KS_STAMP(0);
   constexpr int BN = 16 * NT, RS = BN + 4, QN = BN / 4;
   __shared__ __attribute__((aligned(16))) float red[WV][16][RS];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1179,7 +1167,6 @@ __global__ __launch_bounds__(64 * WV, (KC <= 6 && KC * NT <= 8) ? 4 : 2) void co
   float4 a_cur[KC], a_nxt[KC];
   float4 gq = gate_fetch(rg);
   load_a(rg, a_cur);
-  KS_STAMP(1);
   for (; rg < row_groups; rg += gridDim.x) {
     load_a(rg + gridDim.x, a_nxt);
     if (gated) {   // (uniform)
@@ -1232,9 +1219,7 @@ __global__ __launch_bounds__(64 * WV, (KC <= 6 && KC * NT <= 8) ? 4 : 2) void co
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int j = 0; j < NT; ++j) red[wave][g * 4 + r][j * 16 + l15] = PREC == 2 ? acc[j][r] * out_scale : acc[j][r];
-    if (rg == bx) KS_STAMP(2);
     __syncthreads();
-    if (rg == bx) KS_STAMP(3);
     const int m = rg * 16 + frow;
     if (fcol && m < M) {
       float4 v = ld4(&red[0][frow][fq * 4]);
@@ -1257,22 +1242,11 @@ __global__ __launch_bounds__(64 * WV, (KC <= 6 && KC * NT <= 8) ? 4 : 2) void co
         s2 = f4fma(v, v, s2);
       }
     }
-    if (rg == bx) KS_STAMP(4);
     __syncthreads();   // the staging tile is rewritten by the next row group
 #pragma unroll
     for (int kg = 0; kg < KC; ++kg) a_cur[kg] = a_nxt[kg];
   }
-  KS_STAMP(5);
-#ifdef KS_DBG
-  auto ks_flush = [&]() {
-    KS_STAMP(7);
-    if (p.dbg_stamps != nullptr && threadIdx.x == 0)
-      for (int k = 0; k < 8; ++k) p.dbg_stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + k] = ks_st[k];
-  };
-#else
-  auto ks_flush = [&]() {};
-#endif
-  if (!stats) { ks_flush(); return; }
+  if (!stats) return;
   // column sums over the 16 rows of the finishing threads: through the (now free) staging tile, [v][row][quad]
   float4* fold = reinterpret_cast<float4*>(&red[0][0][0]);
   if (fin) {
@@ -1290,8 +1264,6 @@ __global__ __launch_bounds__(64 * WV, (KC <= 6 && KC * NT <= 8) ? 4 : 2) void co
       st4(p.stats_part + ((long long)bx * 2 + v) * p.Nout + n, a);
     }
   }
-  KS_STAMP(6);
-  ks_flush();
 }
 
 // ------------------------------------------------------------------------------------------------ backward-filter
@@ -1578,11 +1550,9 @@ template <int PREC>
 static void launch_gemm_sk_t(const GemmPlan& g, const ConvGemmParams& p, float* slab, hipStream_t stream) {
   const SkPlan k{g.sk_full, g.sk_rem, g.sk_parts, g.sk_ipp, g.sk_nchunks, g.sk_smax, g.gy, slab};
   dim3 grid(g.sk_full + g.sk_parts), block(256);
-#ifndef GEMM_SK_PF
-#define GEMM_SK_PF 2   // chunks of global loads in flight per thread in the stream-K kernel (3 measured: see profiles/r04_notes.md)
-#endif
+  constexpr int PF = 2;   // chunks of global loads in flight per thread in the stream-K kernel (3 measured: see profiles/r04_notes.md)
 #define SKL(NT_)                                                                                       \
-  hipLaunchKernelGGL((conv_gemm_sk_k<NT_, GEMM_SK_PF, false, PREC>), grid, block, 0, stream, p, k);   \
+  hipLaunchKernelGGL((conv_gemm_sk_k<NT_, PF, false, PREC>), grid, block, 0, stream, p, k);           \
   hipLaunchKernelGGL((sk_fixup_k<NT_>), dim3(g.sk_rem), dim3(1024), 0, stream, p, k);                  \
   break;
   switch (g.nt) {

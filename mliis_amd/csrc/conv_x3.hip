@@ -32,10 +32,7 @@ namespace mliis {
 // (kX3Block = 3072 bytes of one (chunk, 16-column tile) block of a weight image, x3_pack_block: conv_gemm_kernels.hpp -- the weight
 //  shadows of a step, transposes and images, are one launch: mliis_weight_shadows)
 constexpr int kX3BM = 256;       // rows of a workgroup tile (eight waves of 32)
-#ifndef X3_PF
-#define X3_PF 1
-#endif
-constexpr int kX3PF = X3_PF;     // column tiles of B fragments requested ahead of their products
+constexpr int kX3PF = 1;         // column tiles of B fragments requested ahead of their products
 
 // ------------------------------------------------------------------------------------------------ weight images
 // desc rows (int64 [ndesc][8]): {source offset (floats) in `theta`, taps, Cin_total, Cout, ci_begin, Cin (window), mode | first block
@@ -52,9 +49,6 @@ struct X3Params {
                          // border_bias as in conv_gemm_tile; B / ldb / b_tap_stride are not used
   const char* image;     // weight image of this conv and direction (x3_pack_k)
   int ncol16;            // its 16-column tiles
-#ifdef X3_CLK
-  unsigned long long* dbg;   // [workgroups][4]: {shader clock, 100 MHz clock} at the start and the end of the first segment's main loop
-#endif
 };
 
 template <int NT>
@@ -198,7 +192,7 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
   // wave's matrix instructions fill the pipe meanwhile)
   auto compute_split = [&](const char* buf, const float4 (&rs)[2][2]) {
     const char* pb = buf + g * 256 + l15 * 16;
-    // B fragments kX3PF column tiles ahead of their products (-DX3_PF=2 | 3 measured: 79.0 / 80.7 against 79.9 us with one tile ahead on
+    // B fragments kX3PF column tiles ahead of their products (two or three tiles ahead measured 79.0 / 80.7 against 79.9 us with one on
     // the 224 -> 112 conv -- the LDS round trip is not what the slower wave of a SIMD waits for)
     constexpr int PF = kX3PF;
     bf16x8 b3[PF + 1][3];
@@ -211,22 +205,14 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
       }
 #pragma unroll
     for (int jn = 0; jn < NT; ++jn) {
-#if defined(X3_ABL) && (X3_ABL & 2)   // ablation: every column tile multiplies the FIRST tile's fragments (no further LDS reads)
-      if (jn + PF < NT && jn + PF < 2) {
-#else
       if (jn + PF < NT) {
-#endif
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) b3[(jn + PF) % (PF + 1)][pl] = *reinterpret_cast<const bf16x8*>(pb + (jn + PF) * kX3Block + pl * 1024);
       }
 #define X3_MM(PA, PB)                                                                                                           \
   acc[0][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[PA][0], b3[jn % (PF + 1)][PB], acc[0][jn], 0, 0, 0);                \
   acc[1][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[PA][1], b3[jn % (PF + 1)][PB], acc[1][jn], 0, 0, 0);
-#if defined(X3_ABL) && (X3_ABL & 1)   // ablation: one matrix instruction per accumulator instead of six
-      X3_MM(0, 0)
-#else
       X3_MM(2, 0) X3_MM(0, 2) X3_MM(1, 1) X3_MM(1, 0) X3_MM(0, 1) X3_MM(0, 0)
-#endif
 #undef X3_MM
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -234,13 +220,7 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
           uint2& h = sh[k >> 1][k & 1];
           uint2& m = sm_[k >> 1][k & 1];
           uint2& l = sl[k >> 1][k & 1];
-#ifdef X3_NOSPLIT   // ablation: no split arithmetic (wrong numbers: what the loop costs without its vector work)
-          h = make_uint2(__float_as_uint(rs[k >> 1][k & 1].x), __float_as_uint(rs[k >> 1][k & 1].y));
-          m = make_uint2(__float_as_uint(rs[k >> 1][k & 1].z), __float_as_uint(rs[k >> 1][k & 1].w));
-          l = h;
-#else
           split3(rs[k >> 1][k & 1], h, m, l);
-#endif
           // (an empty statement that "uses" the piece here: without it the optimiser sinks the arithmetic to the first real use, the
           // assembly of a3n behind the last matrix instruction)
           asm volatile("" : "+v"(h.x), "+v"(h.y), "+v"(m.x), "+v"(m.y), "+v"(l.x), "+v"(l.y));
@@ -254,13 +234,6 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
       a3n[2][rb] = __builtin_bit_cast(bf16x8, (u32x4){sl[rb][0].x, sl[rb][0].y, sl[rb][1].x, sl[rb][1].y});
     }
   };
-#ifdef X3_CLK
-  const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), cr0 = __builtin_amdgcn_s_memrealtime();
-  unsigned long long c_comp = 0, c_skel = 0, c_bar = 0, c_t = ck0;
-#define X3_TICK(acc_) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - c_t; c_t = n_; } while (0)
-#else
-#define X3_TICK(acc_) do { } while (0)
-#endif
   // ---- main loop: every wave multiplies chunk j and, between its own matrix instructions, splits the A chunk it multiplies next; the
   // A chunk after that and the B chunk after next are in flight meanwhile (requested a whole chunk before their first use)
   const int nper = it1 - it0;
@@ -274,17 +247,10 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
   lds_barrier();
   auto chunk = [&](char* cur, char* nxt, float4 (&rs)[2][2]) {   // rs: the registers holding A of the chunk after this one
     compute_split(cur, rs);
-    X3_TICK(c_comp);
-#if !(defined(X3_ABL) && (X3_ABL & 8))   // (ablation 8: the B tile of the first chunks forever -- no B loads, no LDS stores)
     store_b(nxt);        // B of the next chunk (requested one chunk ago)
     load_b();            // B of the chunk after next
-#endif
-#if !(defined(X3_ABL) && (X3_ABL & 4))   // (ablation 4: the A registers of the prologue forever -- no A loads)
     load_a_into(rs);     // A two chunks after the one just split
-#endif
-    X3_TICK(c_skel);
     lds_barrier();
-    X3_TICK(c_bar);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
@@ -298,24 +264,7 @@ __device__ __forceinline__ void conv_x3_tile(const X3Params& q, char* __restrict
     }
     if (it < nper) chunk(sm, sm + B_BYTES, ra);
   }
-#ifndef X3_NO_DRAIN
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the requests past the last chunk are never consumed: none may outlive the loop)
-#endif
-#ifdef X3_CLK
-  if (q.dbg != nullptr && lane == 0 && (wave & 3) == 0) {
-    unsigned long long* d = q.dbg + ((long long)blockIdx.x * 2 + (wave >> 2)) * 8;
-    if (d[0] == 0) {
-      d[0] = ck0;
-      d[1] = cr0;
-      d[2] = __builtin_amdgcn_s_memtime();
-      d[3] = __builtin_amdgcn_s_memrealtime();
-      d[4] = c_comp;
-      d[5] = c_skel;
-      d[6] = c_bar;
-      d[7] = nper;
-    }
-  }
-#endif
   // ---- the raw partial tile (C/D layout: col = lane & 15, row = 4 * (lane >> 4) + reg) to this segment's slab; x3_fixup_k finishes the tile
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb)
@@ -356,12 +305,8 @@ __global__ __launch_bounds__(512) void conv_x3_k(X3Params q, SkPlan k) {
 #endif
   // Consecutive parts -- the K ranges of one row tile and of its neighbours, i.e. the nine taps over the same A rows -- on ONE XCD, so that
   // they share an L2: fabric reads of the 224 -> 112 conv at 56 x 56 199.2 -> 45.6 MB per launch (rocprofv3 --pmc FETCH_SIZE; algorithmic
-  // 31.5 MB), 78.1 -> 76.0 us with its fix-up, +0.3 % on the step (profiles/r06_notes.md).  -DX3_NO_XCD: the plain order.
-#ifndef X3_NO_XCD
+  // 31.5 MB), 78.1 -> 76.0 us with its fix-up, +0.3 % on the step (profiles/r06_notes.md).
   const int part = (int)xcd_remap(blockIdx.x, gridDim.x);
-#else
-  const int part = blockIdx.x;
-#endif
   int lo = part * k.ipp;
   const int total = k.rem * k.nchunks;
   int hi = lo + k.ipp;
@@ -504,11 +449,7 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
   const int tap = mt ? 0 : bx / cblocks;
   const int ci0 = mt ? 0 : (bx - tap * cblocks) * BCI;
   const int n0 = by * BN;
-#ifdef F3_SAMEBZ   // ablation: every pixel split reads the FIRST pixel range (wrong numbers: the kernel with its operands L2-resident)
-  const int mbeg = 0;
-#else
   const int mbeg = bz * p.rows_per_split;
-#endif
   int mend = mbeg + p.rows_per_split;
   if (mend > M) mend = M;
   const int HW = p.H * p.W;
@@ -593,16 +534,7 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
   constexpr int NP = X_PER_THREAD + D_PER_THREAD;
   uint2 th[NP], tm[NP], tl[NP];
   auto split_piece = [&](int k, const float4 (&rx)[X_PER_THREAD], const float4 (&rd)[D_PER_THREAD]) {
-#ifdef F3_NOSPLIT   // ablation: the loads and the LDS stores of the staging, none of its arithmetic (wrong numbers)
-    {
-      const float4 v_ = k < X_PER_THREAD ? rx[k < X_PER_THREAD ? k : 0] : rd[k >= X_PER_THREAD ? k - X_PER_THREAD : 0];
-      th[k] = make_uint2(__float_as_uint(v_.x), __float_as_uint(v_.y));
-      tm[k] = make_uint2(__float_as_uint(v_.z), __float_as_uint(v_.w));
-      tl[k] = th[k];
-    }
-#else
     split3(k < X_PER_THREAD ? rx[k < X_PER_THREAD ? k : 0] : rd[k >= X_PER_THREAD ? k - X_PER_THREAD : 0], th[k], tm[k], tl[k]);
-#endif
     // (an empty statement that "uses" the piece here: without it the optimiser sinks the arithmetic to the stores behind the loop)
     asm volatile("" : "+v"(th[k].x), "+v"(th[k].y), "+v"(tm[k].x), "+v"(tm[k].y), "+v"(tl[k].x), "+v"(tl[k].y));
   };
@@ -670,18 +602,12 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
 #define X3_MM(PA, PB)                                                                                            \
   acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[PA][0], b3[j & 1][PB], acc[0][j], 0, 0, 0);           \
   acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[PA][1], b3[j & 1][PB], acc[1][j], 0, 0, 0);
-#ifdef F3_NOMFMA   // ablation: the chunk skeleton without its matrix instructions (one per accumulator keeps the fragments live)
-        X3_MM(0, 0)
-#else
         X3_MM(2, 0) X3_MM(0, 2) X3_MM(1, 1) X3_MM(1, 0) X3_MM(0, 1) X3_MM(0, 0)
-#endif
 #undef X3_MM
       }
-#ifndef F3_NOSTAGE
 #pragma unroll
       for (int k = 0; k < NP; ++k)
         if ((k * NTW) / NP == j) split_piece(k, rx, rd);
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -696,9 +622,7 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
   lds_barrier();
   auto trip = [&](char* cur, char* nxt, float4 (&rx)[X_PER_THREAD], float4 (&rd)[D_PER_THREAD]) {   // (rx, rd): the chunk after the one in `cur`
     compute_split(cur, rx, rd);   // + the split of the next chunk
-#ifndef F3_NOSTAGE                // (ablation: no split arithmetic, no LDS stores -- the products run on stale stages)
     store_terms(nxt);             // (zeros after the last chunk: nobody reads them)
-#endif
     load_chunk(rx, rd);           // two chunks after the one just split
     lds_barrier();
   };
@@ -708,9 +632,7 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
     trip(sm + STAGE, sm, rxb, rdb);
   }
   if (it < nchunks) trip(sm, sm + STAGE, rxa, rda);
-#ifndef X3_NO_DRAIN
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (as in conv_x3_tile)
-#endif
 
   const long long Ktot = (long long)p.ntaps * p.C;
 #pragma unroll
@@ -729,8 +651,8 @@ __device__ __forceinline__ void conv_filter_x3_body(const FilterGradParams& p, c
 
 // (Round 5, measured and removed: a form in which a workgroup multiplies the THREE taps of one kernel row per staged chunk -- a chunk
 //  = a segment of one image row, the X window of 32 + 2 dil pixels staged once, dY staged once for three taps, 16 channels x all column
-//  tiles per wave.  Ablations of the one-tap form on the decoder's two 56x56 problems, 178 us as one cold launch
-//  (-DF3_NOMFMA / -DF3_NOSTAGE / -DF3_SAMEBZ): 1 of 6 matrix instructions 116 us; no split arithmetic and no LDS stores 97 us; both
+//  tiles per wave.  Ablations of the one-tap form on the decoder's two 56x56 problems, 178 us as one cold launch:
+//  1 of 6 matrix instructions 116 us; no split arithmetic and no LDS stores 97 us; both
 //  40 us; every workgroup on the same pixels 163 us -- the parts add and traffic is not the bound.  The kernel-row form: 158 us cold,
 //  149 against 151 us inside the step, 3424 / 3416 against 3409 / 3418 images/s: no gain where it counts, 330 lines: not kept.)
 // the problems of one (TMF = 2, NT) group of a FilterBatch as one grid: descriptor table as conv_filter_grad2_batched_k
@@ -785,16 +707,14 @@ struct X3Plan {
 };
 constexpr int kX3MinPart = 4;   // K chunks per stream-K part, at least
 
-#ifndef X3_MAX_NT
-#define X3_MAX_NT 9   // (-DX3_MAX_NT=8: probe builds, round 5's tiling)
-#endif
+constexpr int kX3MaxNT = 9;   // (round 5's tiling stopped at 8)
 static int x3_pick_nt(int Nout) {   // the widest column tile that does not pad the output width by much (as conv_gemm.hip: pick_nt, with a
                                     // stronger pull towards few column tiles)
   int best = 1;
   double best_cost = 1e30;
   const int tiles = (Nout + 15) / 16;
-  for (int nt = 1; nt <= X3_MAX_NT; ++nt) {   // (9: the 136-column backward-data conv of the dilated branch as ONE column tile of 144 -- A loaded and split
-                                      //  once instead of once per 80-column tile: round 6)
+  for (int nt = 1; nt <= kX3MaxNT; ++nt) {   // (9: the 136-column backward-data conv of the dilated branch as ONE column tile of 144 -- A loaded and split
+                                             //  once instead of once per 80-column tile: round 6)
     const int blocks = (tiles + nt - 1) / nt;
     const double cost = (double)(blocks * nt * 16) / (double)Nout * (1.0 + 0.08 * (8 - nt));   // (A is loaded AND split once per column tile)
     if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && nt > best)) {
@@ -846,9 +766,6 @@ static int x3_num_cus() {
 
 static void x3_launch(const X3Plan& g, const X3Params& q_, float* slab, hipStream_t stream) {
   X3Params q = q_;
-#ifdef X3_CLK
-  q.dbg = getenv("MLIIS_X3_STAMPS") ? (unsigned long long*)strtoull(getenv("MLIIS_X3_STAMPS"), nullptr, 0) : nullptr;
-#endif
   const SkPlan k{g.full, g.rem, g.parts, g.ipp, g.nchunks, g.smax, g.gy, slab};
   dim3 grid(g.parts), block(512);
 #define L(NT_)                                                                                  \

@@ -28,9 +28,7 @@
 
 namespace mliis {
 
-#ifndef DWM_STORE_AUX
-#define DWM_STORE_AUX 2   // nt: measured cold at N = 8 (tools/bench_dwmarch.py): 112x112x32 forward 10.8 us plain, 8.5 nt, 9.7 sc1, 9.6 sc0 sc1
-#endif
+constexpr int kDwmStoreAux = 2;   // nt: measured cold at N = 8 (tools/bench_dwmarch.py): 112x112x32 forward 10.8 us plain, 8.5 nt, 9.7 sc1, 9.6 sc0 sc1
 typedef unsigned dwm_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned kDwmOob = 0xFFFFFFF0u;   // beyond num_records of the buffer resource: the load returns zeros and moves no data
 
@@ -42,14 +40,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t dwm_rsrc(const void* p) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x80000000u, 0x00020000);
 }
-
-#ifdef DWM_DBG
-#define DWM_DBG_ON(a, bit) (((a).dbg & (bit)) != 0)
-#define DWM_STAMP(k) do { if (k < 16) stamp[k] = wall_clock64(); } while (0)
-#else
-#define DWM_DBG_ON(a, bit) false
-#define DWM_STAMP(k) do { } while (0)
-#endif
 
 // T = storage type of the tensor behind the resource (float: 16-byte quads; bf16s: 8-byte quads, widened exactly); `off` in BYTES
 typedef unsigned dwm_u32x2 __attribute__((ext_vector_type(2)));
@@ -70,27 +60,22 @@ __device__ __forceinline__ void dwm_store(__amdgpu_buffer_rsrc_t r, int off, boo
     const uint2 pk = pack_bf16x4(v);
     dwm_u32x2 u2;
     u2.x = pk.x; u2.y = pk.y;
-    __builtin_amdgcn_raw_buffer_store_b64(u2, r, ok ? off : (int)kDwmOob, 0, DWM_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(u2, r, ok ? off : (int)kDwmOob, 0, kDwmStoreAux);
     return;
   }
   dwm_u32x4 u;
   u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y); u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
-  // (out of range: dropped by the range check, no branch.)  DWM_STORE_AUX: cache policy of the output stores (gfx950 aux bits:
+  // (out of range: dropped by the range check, no branch.)  kDwmStoreAux: cache policy of the output stores (gfx950 aux bits:
   // 1 = sc0, 2 = nt, 16 = sc1).  Plain stores stay dirty in the XCD's L2 until the end-of-kernel release writes them back in one
   // burst behind the last workgroup (output bytes / ~6 TB/s added to every launch); write-through stores leave while the march runs.
-  __builtin_amdgcn_raw_buffer_store_b128(u, r, ok ? off : (int)kDwmOob, 0, DWM_STORE_AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(u, r, ok ? off : (int)kDwmOob, 0, kDwmStoreAux);
 }
 __device__ __forceinline__ float4 f4sel(bool ok, const float4 v) { return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f); }
 template <typename T> __device__ __forceinline__ float4 dwm_stored(const float4 v) { return stored_value(static_cast<const T*>(nullptr), v); }
 
-// -DDWM_K5_TS2 (experiment of round 6): the 5x5 stride-1 layer with TWO outputs per thread along W instead of four --
-// bands of 14 columns (twice the workgroups), a 5 x 6 window per strip, fewer live registers in the window phase
-#ifndef DWM_K5_TS2
-#define DWM_K5_TS2 0
-#endif
 template <int K, int S>
 struct MarchCfg {
-  static constexpr int TS = (S == 1 && !(K == 5 && DWM_K5_TS2)) ? 4 : 2;   // outputs per thread along W (TS * S input pixels between strips)
+  static constexpr int TS = S == 1 ? 4 : 2;            // outputs per thread along W (TS * S input pixels between strips)
   static constexpr int BW = 7 * TS;                    // produced columns of a band: 7 strips (28 | 14), so that ...
   static constexpr int SPR = BW / TS;
   static constexpr int RS = 4;                         // output rows per step: 4 rows x 8 strip slots = the 32 pixel lanes
@@ -191,10 +176,6 @@ struct DwmArgs {
   int bands, bw, chunks, rpc;   // column bands of bw produced columns, row chunks of rpc produced rows
   float* stats_part;   // forward: [gridDim.x][2][C] {sum y, sum y^2} or null; backward: [gridDim.x][2][C] {sum g, sum g xhat} or null
   DwmBn bn;
-#ifdef DWM_DBG
-  int dbg;             // diagnosis: 1 = no window FMAs, 2 = no global loads, 4 = no stores, 8 = no march (prologue only)
-  unsigned long long* stamps;   // [gridDim.x * gridDim.y][16] wall-clock stamps (100 MHz) of wave 0, or null
-#endif
   DwmDyBn dyb;         // backward with DYBN: x = da2, dyb.z = z1 -- the ring receives dz1, the depthwise batch norm's input gradient
   const float* z;      // backward: the batch norm's input at the produced positions [N,Ho,Wo,C] (plain input when bn.gamma == nullptr)
   float* dw_part;      // backward: [gridDim.x][K*K][C]
@@ -332,11 +313,6 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
   __shared__ float4 wl[K * K * 8];
   __shared__ __attribute__((aligned(16))) float s_mr[64];
 
-#ifdef DWM_DBG
-  unsigned long long stamp[16];
-  for (int k = 0; k < 16; ++k) stamp[k] = 0;
-#endif
-  DWM_STAMP(0);
   const int t = threadIdx.x, q = t & 7, p = t >> 3;
   const unsigned bx = xcd_remap(blockIdx.x, gridDim.x);
   const int chunk = (int)(bx % (unsigned)a.chunks);
@@ -359,7 +335,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
 
   // ---- staging map: pixel lane p <-> ring column p, load j of a batch <-> its row j.  Everything that depends on the row is
   //      wave-uniform (a scalar offset, a scalar predicate), everything per lane is computed once: three instructions per load
-  const bool colok = cok && p < ibw && (unsigned)(ix0 + p) < (unsigned)Wi && !DWM_DBG_ON(a, 2);
+  const bool colok = cok && p < ibw && (unsigned)(ix0 + p) < (unsigned)Wi;
   const int tbase = (((n * Hi + iy0) * Wi + ix0 + p) * C + c) * EA;   // byte offset of ring row 0 at this lane's column ("negative": masked)
   const int rowbytes = Wi * C * EA;
   const int lcol = p < IBWP ? (p ^ ((p >> 2) & 1)) * 8 + q : kTrash + q;   // (lanes beyond the pitch write the spare pixel)
@@ -416,7 +392,6 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
   DwmBnState<!BWD> bst;
   if (PRE) dwm_bn_begin(a.bn, C, c0, q, cok, bst);
   if (DYBN) dq = dwm_dybn_setup(a.dyb, C, c0, q, cok, n, bx == 0);
-  DWM_STAMP(1);
   Batch ra, rb_;
   float4 za[TS], zb[TS];
   {
@@ -430,14 +405,11 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
     issue(ra, WIN);             // step 1
     issue(rb_, WIN + NEW);      // step 2
     issue_z(zb, 1);
-    DWM_STAMP(2);
     if (t < K * K * 8) wl[t] = wreg;
     commit(h0, HEAD, HEAD < 0 ? HEAD + NR : HEAD);
     commit(h1, WIN - NEW, (WIN - NEW) % NR);
   }
-  DWM_STAMP(3);
   __syncthreads();            // (also publishes wl)
-  DWM_STAMP(4);
 
   float4 s1 = f4zero(), s2 = f4zero();
   float4 dwacc[BWD ? K * K : 1];
@@ -511,26 +483,24 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
           if (BWD) dwacc[ky * K + kx] = f4fma(in[u + kx], av[u], dwacc[ky * K + kx]);
         }
     };
-    if (!DWM_DBG_ON(a, 1)) {
-      if (K == 3) {
-        // 3x3: the scheduler may hoist all three rows' reads above the FMAs (18-27 float4: one LDS latency instead of three)
-        float4 in[WW];
+    if (K == 3) {
+      // 3x3: the scheduler may hoist all three rows' reads above the FMAs (18-27 float4: one LDS latency instead of three)
+      float4 in[WW];
 #pragma unroll
-        for (int ky = 0; ky < K; ++ky) {
-          read_row(ky, in);
-          fma_row(ky, in);
-        }
-      } else {
-        // 5x5: two rows in registers -- the reads of row ky + 1 are in flight under the FMAs of row ky; a scheduling fence per row
-        // keeps the compiler from hoisting all K rows (K * WW float4 = 160-220 registers)
-        float4 inA[WW], inB[WW];
-        read_row(0, inA);
+      for (int ky = 0; ky < K; ++ky) {
+        read_row(ky, in);
+        fma_row(ky, in);
+      }
+    } else {
+      // 5x5: two rows in registers -- the reads of row ky + 1 are in flight under the FMAs of row ky; a scheduling fence per row
+      // keeps the compiler from hoisting all K rows (K * WW float4 = 160-220 registers)
+      float4 inA[WW], inB[WW];
+      read_row(0, inA);
 #pragma unroll
-        for (int ky = 0; ky < K; ++ky) {
-          if (ky + 1 < K) read_row(ky + 1, (ky & 1) ? inA : inB);
-          fma_row(ky, (ky & 1) ? inB : inA);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+      for (int ky = 0; ky < K; ++ky) {
+        if (ky + 1 < K) read_row(ky + 1, (ky & 1) ? inA : inB);
+        fma_row(ky, (ky & 1) ? inB : inA);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
     // stores and sums without a branch (a conditional block here makes the compiler sink the FMAs of each output into it and keep the
@@ -541,7 +511,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
     for (int u = 0; u < TS; ++u) {
       const bool ok = row_ok && sx * TS + u < bwa;
       if (!(K == 5 && !BWD)) acc[u] = dwm_stored<TB>(acc[u]);   // (bf16 storage: the sums below see what the consumers will read back)
-      dwm_store<TB>(rY, ybase + u * C * EB, ok && !DWM_DBG_ON(a, 4), acc[u]);
+      dwm_store<TB>(rY, ybase + u * C * EB, ok, acc[u]);
       if (!BWD) {
         const float4 v = f4sel(ok, acc[u]);
         s1 = f4add(s1, v);
@@ -562,19 +532,15 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
   //      step i + 3 are issued; two register sets alternate, so one batch is always in flight under the compute phase
   int rbn = WIN;          // ring row of the first row of the batch for step i + 1
   int sbn = WIN % NR;     // its ring slot
-  for (int i = 0; i < (DWM_DBG_ON(a, 8) ? 0 : nsteps); i += 2) {
+  for (int i = 0; i < nsteps; i += 2) {
     compute(i, za);
-    if (i == 0) DWM_STAMP(5);
     commit(ra, rbn, sbn);
-    if (i == 0) DWM_STAMP(6);
     issue(ra, rbn + 2 * NEW);
     issue_z(za, i + 2);
     rbn += NEW; sbn += NEW; if (sbn >= NR) sbn -= NR;
     sw += NEW; if (sw >= NR) sw -= NR;
     __syncthreads();
-    if (i == 0) DWM_STAMP(7);
     if (i + 1 < nsteps) compute(i + 1, zb);
-    if (i == 0) DWM_STAMP(8);
     commit(rb_, rbn, sbn);
     issue(rb_, rbn + 2 * NEW);
     issue_z(zb, i + 3);
@@ -583,15 +549,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void dwm_conv_k(const DwmArgs a) 
     __syncthreads();
   }
 
-  DWM_STAMP(9);
   if (a.stats_part != nullptr && (!BWD || PRE)) dwm_emit_pair(s1, s2, ring, a.stats_part, bx, C, c0);
-  DWM_STAMP(10);
-#ifdef DWM_DBG
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  DWM_STAMP(11);
-  if (a.stamps != nullptr && t == 0)
-    for (int k = 0; k < 16; ++k) a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 16 + k] = stamp[k];
-#endif
   if (BWD) {
     // filter gradient of this workgroup: butterfly over the 8 pixel lanes of a wave that share a quad, the 4 waves through LDS
     __syncthreads();       // (the statistics fold above used the same LDS)
@@ -890,7 +848,7 @@ static inline MarchGeom march_geom_fwd(int N, int H, int W, int C, int K, int S)
   MarchGeom g;
   same_pad(H, K, S, &g.Ho, &g.pt);
   same_pad(W, K, S, &g.Wo, &g.pl);
-  if (S == 1 && !(K == 5 && DWM_K5_TS2)) march_split(N, ceil_div(C, 32), g.Ho, g.Wo, 4, 28, 4, false, &g);
+  if (S == 1) march_split(N, ceil_div(C, 32), g.Ho, g.Wo, 4, 28, 4, false, &g);
   else march_split(N, ceil_div(C, 32), g.Ho, g.Wo, 4, 14, 2, false, &g);
   return g;
 }
@@ -901,8 +859,7 @@ static inline MarchGeom march_geom_bwd(int N, int H, int W, int C, int K, int S)
   same_pad(H, K, S, &g.Ho, &g.pt);
   same_pad(W, K, S, &g.Wo, &g.pl);
   if (S == 1) {
-    if (K == 5 && DWM_K5_TS2) march_split(N, ceil_div(C, 32), H, W, 4, 14, 2, true, &g);
-    else march_split(N, ceil_div(C, 32), H, W, 4, 28, 4, true, &g);
+    march_split(N, ceil_div(C, 32), H, W, 4, 28, 4, true, &g);
   } else {
     const int py = ((H + g.pt - 1) >> 1) - (g.pt >> 1) + 1, pxn = ((W + g.pl - 1) >> 1) - (g.pl >> 1) + 1;
     march_split(N, ceil_div(C, 32), py, pxn, 2, 14, 1, true, &g);
@@ -1026,10 +983,6 @@ int mliis_dwconv_bn_fwd(const float* z, const float* bn_part, int bn_nblk, const
   a.Hi = H; a.Wi = W; a.Ho = g.Ho; a.Wo = g.Wo; a.C = C; a.pt = g.pt; a.pl = g.pl;
   a.bands = g.bands; a.bw = g.bw; a.chunks = g.chunks; a.rpc = g.rpc;
   a.stats_part = stats_part;
-#ifdef DWM_DBG
-  a.dbg = getenv("MLIIS_DWM_DBG") ? atoi(getenv("MLIIS_DWM_DBG")) : 0;
-  a.stamps = getenv("MLIIS_DWM_STAMPS") ? (unsigned long long*)strtoull(getenv("MLIIS_DWM_STAMPS"), nullptr, 0) : nullptr;
-#endif
   if (pre) a.bn = make_bn(bn_part, bn_nblk, (long long)N * H * W, bn_gamma, bn_beta, bn_mean, bn_rstd, bn_moving_mean, bn_moving_var, eps, momentum, 0);
 #define DWM_FWD(K_, S_)                                             \
   do {                                                              \

@@ -135,9 +135,6 @@ __global__ __launch_bounds__(256) void resize_bwd_k(const float* __restrict__ dy
 // quad), its candidate rows are loaded RB at a time (128-byte lines, all in flight); phase 2 folds the candidate columns of every
 // input column out of LDS.  An output row feeds two input rows, so dy crosses L2 ~2x instead of the ~7.5x of the gather form (a 4x
 // upsample), and the chain is one round of loads + one barrier.  Deterministic (fixed loop orders, no atomics).
-#ifndef RESIZE_BWD_ROWS
-#define RESIZE_BWD_ROWS 1   // 0: the gather form for every shape (A/B: tools/build_variants.sh)
-#endif
 constexpr int kResizeRowsThreads = 512;
 template <int RB>
 __global__ __launch_bounds__(kResizeRowsThreads) void resize_bwd_rows_k(const float* __restrict__ dy, int lddy, float* __restrict__ dx,
@@ -663,7 +660,7 @@ int mliis_resize_bilinear_bwd(const float* dy, int lddy, float* dx, int lddx, in
                 "resize_bilinear_bwd: bad shape (input side must be > 1)");
   const float sh = (float)(Hi - 1) / (float)(Ho - 1), sw = (float)(Wi - 1) / (float)(Wo - 1);
   if ((C & 3) == 0 && (lddx & 3) == 0 && (lddy & 3) == 0 && aligned16(dx) && aligned16(dy)) {
-    if (RESIZE_BWD_ROWS && C >= 16 && Wo <= 512 && Hi <= 65535 && N <= 65535) {   // separable form: one workgroup per (32-channel group, input row, image)
+    if (C >= 16 && Wo <= 512 && Hi <= 65535 && N <= 65535) {   // separable form: one workgroup per (32-channel group, input row, image)
       const dim3 grid((unsigned)((C + 31) / 32), (unsigned)Hi, (unsigned)N);
       const size_t lds = (size_t)Wo * 8 * sizeof(float4);
       if (2.f / sh + 3.f > 4.f)

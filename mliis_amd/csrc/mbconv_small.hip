@@ -16,8 +16,8 @@
 // filter row) pairs.  Wave-level sums are DPP adds (VALU), not LDS permutes.  Eligible: stride 1, N*H*W <= 2048 pixels,
 // N*ceil(H/4)*W <= 512 strips, C % 4 == 0 -- anything else takes the op-by-op path.
 //
-// Round 4 -- V channels per workgroup, V = 4 (quads) or 2 (pairs), chosen per layer (sm_group_width), and a stamps build (-DSM_DBG,
-// profiles/r04_notes.md) that showed where the 10-23 us of a launch go.  Rounds 2-3 ran quads only: 120 / 168 workgroups on 256 CUs.
+// Round 4 -- V channels per workgroup, V = 4 (quads) or 2 (pairs), chosen per layer (sm_group_width), and a stamps build
+// (profiles/r04_notes.md) that showed where the 10-23 us of a launch go.  Rounds 2-3 ran quads only: 120 / 168 workgroups on 256 CUs.
 // Filling the chip with 240 / 336 workgroups of pairs does NOT shorten the memory phases -- a workgroup touches the same 1568 lines
 // per tensor whatever V is, 8-byte accesses run at 0.55-0.7 of the 16-byte rate, and channel triples (12-byte accesses) were 1.3-1.8x
 // slower -- so pairs are used only where the compute phases dominate: the 5x5 layers whose C / 2 workgroups fit one round (25 taps:
@@ -40,23 +40,6 @@ constexpr int kSmMaxPix = 2048;    // N*H*W: two [N*H*W] tiles of <= 16-byte slo
 struct SmallGeom {
   int N, H, W, C, HS, nitems, npix;
 };
-
-// -DSM_DBG (diagnosis builds only, tools/_exp): wall-clock stamps (100 MHz) of thread 0 at the phase boundaries of both kernels
-#ifdef SM_DBG
-#define SM_STAMP_DECL unsigned long long stamp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define SM_STAMP(k) do { stamp[k] = wall_clock64(); } while (0)
-#define SM_STAMP_FLUSH(ptr)                                                              \
-  do {                                                                                   \
-    __builtin_amdgcn_s_waitcnt(0);                                                       \
-    stamp[11] = wall_clock64();                                                          \
-    if (threadIdx.x == 0 && (ptr) != nullptr)                                            \
-      for (int k = 0; k < 12; ++k) (ptr)[(long long)blockIdx.x * 12 + k] = stamp[k];     \
-  } while (0)
-#else
-#define SM_STAMP_DECL
-#define SM_STAMP(k) do { } while (0)
-#define SM_STAMP_FLUSH(ptr) do { } while (0)
-#endif
 
 // ---- V channels of one pixel: plain float arrays, every operation an unrolled loop (V = 2, 3, 4)
 template <int V>
@@ -289,9 +272,6 @@ struct SmallFwd {
   int z1_blocked;       // != 0: z1 is written in the group-blocked layout (only the backward kernel of the same layer reads it)
   SmallGeom g;
   float eps, one_minus_momentum;
-#ifdef SM_DBG
-  unsigned long long* stamps;
-#endif
 };
 
 // taps in registers (fully unrolled window loop) where K*K*V floats fit beside the window: every form but the 5x5 quads
@@ -311,8 +291,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
   float* stat = reinterpret_cast<float*>(fold + 8);                      // mean0[4] rstd0[4] var0[4]
   const int cq = sm_channel_group<V>(g.C);
   if (cq < 0) return;
-  SM_STAMP_DECL;
-  SM_STAMP(0);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c = cq * V;
   const SmStrip st = sm_strip(g, c, (int)sizeof(T), V);
@@ -350,9 +328,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
     mmv1 = p.mm1[c + t];
     mvv1 = p.mv1[c + t];
   }
-  SM_STAMP(1);
   __syncthreads();
-  SM_STAMP(2);
   if (t < V) {
     const double s1 = fold[t], s2 = fold[V + t];
     const double inv_n = 1.0 / (double)g.npix;
@@ -364,7 +340,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
     stat[8 + t] = (float)var;
   }
   __syncthreads();
-  SM_STAMP(3);
   const VT m0 = vld<V>(stat), r0 = vld<V>(stat + 4);
   {
     const VT ga = vld<V>(p.gamma0 + c), be = vld<V>(p.beta0 + c);
@@ -379,7 +354,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
     }
   }
   __syncthreads();
-  SM_STAMP(4);
   // ---- depthwise stencil out of LDS: outputs (h0 + j, w), j < 4; TF-SAME, stride 1.  Window row r (image row h0 - P + r) is read once
   //      and feeds the (output row j, filter row ky = r - j) pairs.
   constexpr int P = (K - 1) / 2;
@@ -452,9 +426,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (st.ok(j)) s1 = vadd(s1, acc[j]);
-  SM_STAMP(5);
   sm_block_sum2<V>(s1, s2, red);
-  SM_STAMP(6);
   const float inv_n = 1.0f / (float)g.npix;
   const VT m1 = vscale(s1, inv_n);
   VT d2 = vzero<V>(), dummy = vzero<V>();
@@ -465,7 +437,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
       d2 = vfma(d, d, d2);
     }
   sm_block_sum2<V>(d2, dummy, red);
-  SM_STAMP(7);
   const VT var1 = vscale(d2, inv_n);
   VT r1;
   SMV_FOR r1.v[i] = 1.0f / sqrtf(var1.v[i] + p.eps);
@@ -485,7 +456,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
     for (int j = 0; j < 4; ++j) sm_st<V, T>(ra1, st.poff(j), a1v[j]);
   }
   sm_lds_barrier();
-  SM_STAMP(8);
   // image n owns strips [n * HS * W, (n + 1) * HS * W): one wave per image (fixed order), DPP wave sum
   {
     const int per = g.HS * g.W;
@@ -496,7 +466,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
       if (lane == 63) vst<V>(p.s + (long long)img * g.C + c, vscale(a, 1.0f / (float)(g.H * g.W)));
     }
   }
-  SM_STAMP(9);
   // ---- batch statistics for the backward pass, moving averages (biased variance: non-fused TpuBatchNormalization, utils.py:87-134)
   if (t < V) {
     const float mf = stat[t], vf = stat[8 + t];
@@ -519,8 +488,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_fwd_small_k(SmallFwd p) 
       p.mv1[c + t] = mvv1 - (mvv1 - v1t) * p.one_minus_momentum;
     }
   }
-  SM_STAMP(10);
-  SM_STAMP_FLUSH(p.stamps);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -538,9 +505,6 @@ struct SmallBwd {
   const float* z0b;        // nullable: z0 in the group-blocked layout (mbconv_dw_fwd_small's z0b), read instead of z0
   int z1_blocked;          // bit 0: z1 is in the group-blocked layout; bit 1: so is da2 (mliis_conv2d_bwd_data_gate, MLIIS_DT_BLOCKED)
   SmallGeom g;
-#ifdef SM_DBG
-  unsigned long long* stamps;
-#endif
 };
 
 template <int K, int V, typename T = float>   // T: storage type of da2, z1, z0 and dz0
@@ -561,8 +525,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
   float* tileX = wred + kSmWaves * K * K * F;              // [npix] slots (PARK only): xhat0                 // [kSmWaves][K*K] slots: filter-gradient partials
   const int cq = sm_channel_group<V>(g.C);
   if (cq < 0) return;
-  SM_STAMP_DECL;
-  SM_STAMP(0);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c = cq * V;
   const SmStrip st = sm_strip(g, c, (int)sizeof(T), V);
@@ -598,9 +560,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
       s1 = vadd(s1, gg);
       s2 = vfma(gg, xh, s2);
     }
-    SM_STAMP(1);
     sm_block_sum2<V>(s1, s2, red);
-    SM_STAMP(2);
     if (t == 0) {
       vst<V>(p.dbeta1 + c, s1);
       vst<V>(p.dgamma1 + c, s2);
@@ -622,7 +582,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
     if (PARK && st.ok(j)) lds_st<V>(tileX, (st.n * g.H + st.h0 + j) * g.W + st.w, xh);
   }
   __syncthreads();
-  SM_STAMP(3);
   constexpr int P = (K - 1) / 2;
   // ---- depthwise filter gradient: dw[ky][kx] = sum_pixels a0[h + ky - P][w + kx - P] * dz1[h][w]; window row r (image row h0 - P + r)
   //      read once for its (j, ky = r - j) pairs; K*K accumulators, DPP wave sums, the 8 waves through LDS
@@ -653,7 +612,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
         if (K == 5) __builtin_amdgcn_sched_barrier(0);
       }
     }
-    SM_STAMP(4);
 #pragma unroll
     for (int i = 0; i < K * K; ++i) {
       const VT v = sm_wave_sum63(wacc[i]);
@@ -661,7 +619,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
     }
   }
   __builtin_amdgcn_sched_barrier(0);   // (the backward-data phase's taps / window loads must not be hoisted above the K*K accumulators' end)
-  SM_STAMP(5);
   // ---- depthwise backward-data out of LDS: da0[h][w] = sum dz1[h + P - ky][w + P - kx] * w[ky][kx]  (stride 1, SAME: P = (K-1)/2)
   VT acc[4];
 #pragma unroll
@@ -708,9 +665,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
       for (int r = 0; r < K + 3; ++r) body(r);
     }
   }
-  SM_STAMP(6);
   __syncthreads();   // (the filter-gradient partials of all waves are in LDS)
-  SM_STAMP(7);
   if (t < K * K) {
     VT v = lds_ld<V>(wred, t);
 #pragma unroll
@@ -740,9 +695,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
       s1 = vadd(s1, gg);
       s2 = vfma(gg, z0v[j], s2);
     }
-    SM_STAMP(8);
     sm_block_sum2<V>(s1, s2, red);
-    SM_STAMP(9);
     if (t == 0) {
       vst<V>(p.dbeta0 + c, s1);
       vst<V>(p.dgamma0 + c, s2);
@@ -753,8 +706,6 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
     for (int j = 0; j < 4; ++j)
       if (st.ok(j)) sm_st<V, T>(rdz, st.poff(j), vbn_dx(acc[j], z0v[j], a, b, ga0, r0));
   }
-  SM_STAMP(10);
-  SM_STAMP_FLUSH(p.stamps);
 }
 #undef SMV_FOR
 
@@ -856,9 +807,6 @@ int mliis_mbconv_dw_fwd_small(const float* z0, const float* part0, int nblk0, co
   MLIIS_REQUIRE(aligned16(z0_blocked), MLIIS_ERR_ALIGN, "mbconv_dw_fwd_small: z0_blocked must be 16-byte aligned");
   SmallFwd p{z0, part0, nblk0, gamma0, beta0, mean0, rstd0, moving_mean0, moving_var0, w, gamma1, beta1, mean1, rstd1, moving_mean1,
              moving_var1, a0, z1, a1, s, z0_blocked, z1_blocked, g, eps, 1.0f - momentum};
-#ifdef SM_DBG
-  p.stamps = getenv("MLIIS_SM_STAMPS") ? reinterpret_cast<unsigned long long*>(strtoull(getenv("MLIIS_SM_STAMPS"), nullptr, 10)) : nullptr;
-#endif
   const size_t lds = small_fwd_lds(g, k);
   int rc;
   MLIIS_REQUIRE(act_dtype == MLIIS_DT_F32 || act_dtype == MLIIS_DT_BF16, MLIIS_ERR_ARG, "mbconv_dw_fwd_small: bad act_dtype");
@@ -890,9 +838,6 @@ int mliis_mbconv_dw_bwd_small(const float* da2, const float* gate, const float* 
   MLIIS_REQUIRE(aligned16(z0_blocked), MLIIS_ERR_ALIGN, "mbconv_dw_bwd_small: z0_blocked must be 16-byte aligned");
   SmallBwd p{da2, gate, chan_add, z1, mean1, rstd1, gamma1, beta1, w, z0, mean0, rstd0, gamma0, beta0, dgamma1, dbeta1, dw, dgamma0, dbeta0,
              dz0, z0_blocked, z1_blocked, g};
-#ifdef SM_DBG
-  p.stamps = getenv("MLIIS_SM_STAMPS") ? reinterpret_cast<unsigned long long*>(strtoull(getenv("MLIIS_SM_STAMPS"), nullptr, 10)) : nullptr;
-#endif
   const size_t lds = small_bwd_lds(g, k);
   int rc;
   MLIIS_REQUIRE(act_dtype == MLIIS_DT_F32 || act_dtype == MLIIS_DT_BF16, MLIIS_ERR_ARG, "mbconv_dw_bwd_small: bad act_dtype");

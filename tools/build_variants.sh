@@ -9,7 +9,7 @@ make -j8 >/dev/null
 OUT=../../tools/_alt
 mkdir -p $OUT
 FLAGS="-O3 -std=c++17 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-variable -fno-slp-vectorize"
-SRC=${SRC:-conv_x3}       # the translation unit rebuilt under the switch (SRC=dwmarch tools/build_variants.sh "ts2:-DDWM_K5_TS2=1")
+SRC=${SRC:-conv_x3}       # the translation unit rebuilt under the switch (SRC=dwmarch tools/build_variants.sh "name:-Dflag ...")
 [ $SRC = conv_x3 ] || FLAGS=${FLAGS/ -fno-slp-vectorize/}
 OBJS=$(ls *.o | grep -v $SRC.o)
 # further variants: tools/build_variants.sh "name:-Dflag ..." ...

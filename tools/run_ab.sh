@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library variants (tools/build_variants.sh "name:-Dflag") on the headline step: the variants alternate REPS times
 # (box-to-box spread is +-1 %, so only runs of one call compare).  Optional TESTS="tests/test_ops_gpu.py -k resize" first, per variant.
-#   VARIANTS="base norows" REPS=3 bash tools/run_ab.sh        -> gpurun_out/ab/ab.txt
+#   VARIANTS="base noclaim" REPS=3 bash tools/run_ab.sh       -> $O/ab.txt
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/ab
 mkdir -p $O

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Variants of conv_x3_k (tools/build_variants.sh "name:-Dflag"): parity (tests/test_x3_gpu.py), launch time of the decoder's convs
 # (tools/x3_probe.py, host-timed with the fix-up launch), fabric read traffic of the 224 -> 112 conv (rocprofv3 --pmc FETCH_SIZE, its own
-# pass) and the step.   VARIANTS="base xcd k64" bash tools/run_x3_variants.sh     -> gpurun_out/x3var/
+# pass) and the step.   VARIANTS="base noclaim" bash tools/run_x3_variants.sh     -> $O/
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/x3var
 mkdir -p $O
 cd $R
-for V in ${VARIANTS:-base xcd k64 xcdk64}; do
+for V in ${VARIANTS:-base noclaim}; do
   if [ $V = base ]; then unset MLIIS_HIP_LIB; else export MLIIS_HIP_LIB=$R/tools/_alt/libmliis_$V.so; fi
   echo "== $V"
   python -m pytest tests/test_x3_gpu.py -q -x 2>&1 | tail -1
