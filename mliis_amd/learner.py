@@ -99,9 +99,6 @@ class Learner(_Passes):
         self._idx_pin = torch.empty((16, 64), dtype=torch.int32).pin_memory()
         self._idx_ev = [None] * 16
         self._idx_n = 0
-        self._idx_by_kernel = os.environ.get("MLIIS_IDX_MEMCPY", "0") != "1"
-        self.stem_stats = os.environ.get("MLIIS_STEM_STATS", "1") != "0"   # the stem conv's launch also emits its batch norm's stage-1 sums
-        self.defer_loss_fold = os.environ.get("MLIIS_NO_DEFER_LOSS_FOLD", "0") != "1"
         self.arena = Arena(self.arch, self.device)
         self.arena.init_weights(seed)
         self.variables_initialized = True
@@ -112,23 +109,19 @@ class Learner(_Passes):
         A = self.arena
         self.theta_t = torch.zeros_like(A.theta)
         fe = self.arch.name
-        desc = []
-        for p in A.trainable:
-            if p.kind == "conv" and p.executed and "/se/" not in p.name and p.name not in (f"{fe}/stem/conv2d/kernel", "decode/final_layer_weights/kernel"):
-                desc.append([A.t_off[p.name], p.shape[0] * p.shape[1], p.shape[2], p.shape[3]])
-        n_dense = len(desc)
+        dense = [p for p in A.trainable if p.kind == "conv" and p.executed and "/se/" not in p.name and
+                 p.name not in (f"{fe}/stem/conv2d/kernel", "decode/final_layer_weights/kernel")]
+        desc = [[A.t_off[p.name], p.shape[0] * p.shape[1], p.shape[2], p.shape[3]] for p in dense]
         for p in A.trainable:   # the squeeze-excite reduce weights [C, R] too: the MLP's backward reads a column of them per channel
             if p.kind == "conv" and p.executed and p.name.endswith("/se/conv2d/kernel"):
                 desc.append([A.t_off[p.name], 1, p.shape[2], p.shape[3]])
         self.wt_desc = torch.tensor(desc, dtype=torch.int32, device=self.device)
         self.wt_tiles = ops.transpose_tiles(desc)
         # fp8 mode: max |w| of every dense-conv weight, refreshed by the same launch that refreshes the shadow copies
-        self.w_amax = torch.zeros(len(desc), dtype=torch.float32, device=self.device) if matmul_precision == "fp8" else None   # ([:n_dense] used)
+        self.w_amax = torch.zeros(len(desc), dtype=torch.float32, device=self.device) if matmul_precision == "fp8" else None   # ([:len(dense)] used)
         self._amax_of = {}
         if self.w_amax is not None:
-            names = [p.name for p in A.trainable if p.kind == "conv" and p.executed and "/se/" not in p.name and
-                     p.name not in (f"{fe}/stem/conv2d/kernel", "decode/final_layer_weights/kernel")]
-            self._amax_of = {n: self.w_amax[i:i + 1] for i, n in enumerate(names)}
+            self._amax_of = {p.name: self.w_amax[i:i + 1] for i, p in enumerate(dense)}
         self.wt = {p.name: self.theta_t[A.t_off[p.name]:A.t_off[p.name] + p.size] for p in A.trainable}
         self.lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=self.device)
         self._lr_dev_val = float(self.lr)
@@ -152,14 +145,15 @@ class Learner(_Passes):
             self._aug_ev = [None] * 4
             self._aug_n = 0
         self.n_shots = 0
+        self._aug_valid = 0   # samples of the last augment_batch() behind the resident shots (load_task() invalidates them)
         # device RNG of the stochastic ops (drop-connect, dropout): Philox state advanced by the mask kernel itself (csrc/rng.hip)
         # `seed` is the same on every rank (the weights must start identical); `rng_stream` -- the rank -- goes into the high word of
         # the Philox KEY only, so ranks that step in lock-step on different tasks do not draw identical drop-connect / dropout masks
         self.rng_state = ops.rng_state((int(seed) & 0xFFFFFFFF) ^ ((int(rng_stream) & 0xFFFFFFFF) << 32) if rng_stream else seed, self.device)
-        ex_ = [b for b in self.arch.blocks if b.executed and b.skip]
-        self._dc_keeps = torch.tensor([1.0 - b.drop_rate for b in ex_] or [1.0], dtype=torch.float32, device=self.device)
+        self._dc_keeps = torch.tensor([1.0 - b.drop_rate for b in self.arch.executed() if b.skip] or [1.0], dtype=torch.float32, device=self.device)
         self.drop_keep_dev = torch.tensor([1.0 - self.final_layer_dropout_rate], dtype=torch.float32, device=self.device)
         self._drop_keep_val = 1.0 - self.final_layer_dropout_rate
+        self._rng_now = None   # (generator state, mask plan) of a training step that draws its masks: set by _train_sequence, taken by _forward
         self._pname()
         # fp32x3: weight images of the decoder's 3x3 convs (the dilated branch over the whole concat, the fuse conv over its convolved
         # channels), both directions, re-split once per step beside the shadow transpose
@@ -183,9 +177,7 @@ class Learner(_Passes):
         fe = self.arch.name
         self.n_stem = (f"{fe}/stem/conv2d/kernel", f"{fe}/stem/tpu_batch_normalization")
         self.n_blocks = []
-        for b in self.arch.blocks:
-            if not b.executed:
-                continue
+        for b in self.arch.executed():
             s = f"{fe}/blocks_{b.idx}"
             bns = [f"{s}/tpu_batch_normalization", f"{s}/tpu_batch_normalization_1", f"{s}/tpu_batch_normalization_2"]
             cvs = [f"{s}/conv2d/kernel", f"{s}/conv2d_1/kernel"]
@@ -360,12 +352,9 @@ class Learner(_Passes):
         self.stream.synchronize()
         self.x3 = None
         self.x3_on = False
+        for P in self._destroy_graphs():
+            P.steps_run = 0
         for P in self.plans.values():
-            if P.graphs:
-                for gexec in P.graphs.values():
-                    lib.call("mliis_graph_destroy", gexec)
-                P.graphs = {}
-                P.steps_run = 0
             P.wbatch_ready = False   # (the deferred filter-gradient batch is launched with the learner's precision: rebuilt)
 
     def _on_workspace_grow(self, floats: int):
@@ -374,12 +363,17 @@ class Learner(_Passes):
         if self._capturing:
             raise MliisError("workspace would grow to {} floats during HIP-graph capture (the eager first step of a plan sizes it)".format(floats))
         self.stream.synchronize()
-        for P in self.plans.values():
-            if P.graphs:
-                for gexec in P.graphs.values():
-                    lib.call("mliis_graph_destroy", gexec)
-                P.graphs = {}
-                P.steps_run = 0   # next step eager (re-sizes), the one after captures
+        for P in self._destroy_graphs():
+            P.steps_run = 0   # next step eager (re-sizes), the one after captures
+
+    def _destroy_graphs(self) -> List[_Plan]:
+        """Destroy every captured graph of every plan; returns the plans that had any."""
+        had = [P for P in self.plans.values() if P.graphs]
+        for P in had:
+            for gexec in P.graphs.values():
+                lib.call("mliis_graph_destroy", gexec)
+            P.graphs = {}
+        return had
 
     # ------------------------------------------------------------------------------------------- task data
     def load_task(self, images, labels):
@@ -476,17 +470,12 @@ class Learner(_Passes):
         hd_, H_ = self.arch.h_dec, self.arch.image_size
         head_fused = bool(self.fuse_head and not self.dice and not self.darc1 and lib.size("mliis_head_ce_fused_supported", hd_, hd_, H_, H_))
         logits = self._forward(P, self.shots_x, P.idx, True, upsample=not head_fused)
-        P.head_fin = None
-        if head_fused:
-            H = self.arch.image_size
-            if self.defer_loss_fold:   # ONE launch: the fold of the loss partials rides in the final conv's backward-data launch (passes.py)
-                if getattr(P, "head_ws", None) is None:
-                    P.head_ws = ops.Workspace(self.device, lib.size("mliis_head_ce_fused_workspace_floats", P.N, hd_, hd_))
-                _, _, buf = ops.head_ce_fused(P.small, self.shots_y, P.idx, (H, H), self.label_smoothing, P.dsmall, P.loss_out, ws=P.head_ws,
-                                              finalize=False)
-                P.head_fin = (buf, (H, H), 0.0, P.loss_out)
-            else:
-                ops.head_ce_fused(P.small, self.shots_y, P.idx, (H, H), self.label_smoothing, P.dsmall, P.loss_out, ws=self.ws)
+        if head_fused:   # ONE launch: the fold of the loss partials rides in the final conv's backward-data launch (passes.py)
+            if P.head_ws is None:
+                P.head_ws = ops.Workspace(self.device, lib.size("mliis_head_ce_fused_workspace_floats", P.N, hd_, hd_))
+            _, _, buf = ops.head_ce_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, P.dsmall, P.loss_out, ws=P.head_ws,
+                                          finalize=False)
+            P.head_fin = (buf, (H_, H_), 0.0, P.loss_out)
         else:
             ops.softmax_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.dice, 0.0, want_grad=True, want_pred=False,
                            dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
@@ -504,7 +493,7 @@ class Learner(_Passes):
         N = len(batch_idx)
         if N == 0:
             raise ValueError("empty mini-batch")
-        lim = self.max_shots + self._aug_valid if getattr(self, "_aug_valid", 0) else self.n_shots
+        lim = self.max_shots + self._aug_valid if self._aug_valid else self.n_shots
         if min(batch_idx) < 0 or max(batch_idx) >= lim or any(self.n_shots <= i < self.max_shots for i in batch_idx):
             raise ValueError("batch index out of range of the resident task ({} shots)".format(self.n_shots))
         P = self._plan(N)
@@ -518,10 +507,7 @@ class Learner(_Passes):
                     self._idx_ev[slot] = torch.cuda.Event()
                 src = self._idx_pin[slot, :N]
                 src.copy_(torch.tensor(list(batch_idx), dtype=torch.int32))
-                if self._idx_by_kernel:    # one small kernel reading the pinned slot: no copy engine between two steps
-                    ops.copy_words(src, P.idx)
-                else:
-                    P.idx.copy_(src, non_blocking=True)
+                ops.copy_words(src, P.idx)   # one small kernel reading the pinned slot: no copy engine between two steps
                 self._idx_ev[slot].record(self.stream)
             else:
                 P.idx.copy_(torch.tensor(list(batch_idx), dtype=torch.int32), non_blocking=True)
@@ -571,9 +557,8 @@ class Learner(_Passes):
         if P.aspp is not None and aspp_masks is not None:   # four tf.layers.dropout(rate=0.5) sites: scale 0 or 1/keep
             for i, mbuf in enumerate(P.aspp["masks"]):
                 mbuf.copy_(torch.as_tensor(aspp_masks[i], dtype=torch.float32).reshape(mbuf.shape))
-        ex = [b for b in self.arch.blocks if b.executed]
         if self.drop_connect and dc_scales is not None:
-            for b, B in zip(ex, P.blocks):
+            for b, B in zip(self.arch.executed(), P.blocks):
                 if b.skip and "dc" in B:
                     v = dc_scales.get(b.idx)
                     if v is None:
@@ -609,10 +594,7 @@ class Learner(_Passes):
     def close(self):
         """Destroy the captured HIP graphs (the buffers themselves are torch tensors and go with the object)."""
         self.synchronize()
-        for P in self.plans.values():
-            for gexec in P.graphs.values():
-                lib.call("mliis_graph_destroy", gexec)
-            P.graphs = {}
+        self._destroy_graphs()
 
     def gradients_packed(self) -> torch.Tensor:
         return self.arena.export_grad_packed()

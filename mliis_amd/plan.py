@@ -35,13 +35,11 @@ class _Plan:
         self.z_stem, self.a_stem = buf(N, hs, hs, a.stem_out), None   # (a_stem: only when block 0 does not take the stem's BN + swish, below)
         self.st_stem = vec(a.stem_out)
         self.blocks = []
-        nskip = sum(1 for b in a.blocks if b.executed and b.skip)
+        nskip = sum(1 for b in a.executed() if b.skip)
         self.dc_all = torch.ones(max(nskip, 1), N, dtype=torch.float32, device=dev)
         si = 0
         gmax = 0
-        for b in a.blocks:
-            if not b.executed:
-                continue
+        for b in a.executed():
             B = {}
             hi, ho, ce = b.h_in, b.h_out, b.cexp
             # small maps (14x14 at 224x224 inputs): the depthwise half of the block runs as ONE launch per direction (mbconv_small.hip)
@@ -80,7 +78,7 @@ class _Plan:
             B["da0"] = xbuf(N, hi, hi, ce) if b.expand != 1 else buf(N, hi, hi, ce)
             self.blocks.append(B)
         self.dstem = buf(N, hs, hs, a.stem_out)
-        ex0 = [b for b in a.blocks if b.executed]
+        ex0 = a.executed()
         # block 0 without an expand conv (EfficientNet-B0 ... B7) takes the stem's BN + swish into its depthwise launch: the activated
         # stem output is only read there (no identity skip), so it is never written
         self.fuse_stem = bool(ex0 and self.blocks[0]["march"] and ex0[0].expand == 1 and not ex0[0].skip)
@@ -126,12 +124,13 @@ class _Plan:
         self.logits, self.dlogits, self.pred = buf(N, H, H, 2), buf(N, H, H, 2), buf(N, H, H, 2)
         self.drop_mask = buf(N, hd, hd, a.c_final) if L.final_layer_dropout_rate > 0 else None
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
+        # the fused head launch's workspace (the first step that takes it allocates it) and its hand-over to the final conv's backward-data
+        self.head_ws = self.head_fin = None
         # stage-1 BN statistics handed from a producer (GEMM epilogue / stats kernel) to the fused fold+apply kernel
         need = 0
-        for b in a.blocks:
-            if b.executed:
-                for rows, c in ((N * b.h_in ** 2, b.cexp), (N * b.h_out ** 2, b.cexp), (N * b.h_out ** 2, b.cout)):
-                    need = max(need, -(-rows // 16) * 2 * c, ops.bn_stats_partial_floats(rows, c))
+        for b in a.executed():
+            for rows, c in ((N * b.h_in ** 2, b.cexp), (N * b.h_out ** 2, b.cexp), (N * b.h_out ** 2, b.cout)):
+                need = max(need, -(-rows // 16) * 2 * c, ops.bn_stats_partial_floats(rows, c))
         for m in a.rsd:
             need = max(need, -(-(N * m.h * m.h) // 16) * 2 * m.c_out, ops.bn_stats_partial_floats(N * m.h * m.h, m.c_out))
         if a.skipdec is not None:
@@ -143,10 +142,9 @@ class _Plan:
         # the row-marching depthwise kernels (ops.dwconv_bn_fwd / _bwd) READ the producer's partial sums from stats_part while other
         # workgroups of the same launch already WRITE theirs: a second buffer
         need2 = 0
-        for b in a.blocks:
-            if b.executed:
-                need2 = max(need2, lib.raw("mliis_dwconv_bn_fwd_blocks")(N, b.h_in, b.h_in, b.cexp, b.k, b.stride) * 2 * b.cexp,
-                            lib.raw("mliis_dwconv_bn_bwd_blocks")(N, b.h_in, b.h_in, b.cexp, b.k, b.stride) * 2 * b.cexp)
+        for b in a.executed():
+            need2 = max(need2, lib.raw("mliis_dwconv_bn_fwd_blocks")(N, b.h_in, b.h_in, b.cexp, b.k, b.stride) * 2 * b.cexp,
+                        lib.raw("mliis_dwconv_bn_bwd_blocks")(N, b.h_in, b.h_in, b.cexp, b.k, b.stride) * 2 * b.cexp)
         for m in a.rsd:   # (and the second RSD branch GEMM's statistics, folded together with the first's by ops.bn_apply_fused_pair)
             need2 = max(need2, -(-(N * m.h * m.h) // 16) * 2 * m.c_out, ops.bn_stats_partial_floats(N * m.h * m.h, m.c_out))
         self.stats_part2 = buf(need2 + 64)
@@ -154,18 +152,18 @@ class _Plan:
         # conv folds them while its own workgroups already write the next batch norm's into stats_part.  bn2_deferred[i]: block i's
         # project batch norm (+ drop-connect, + identity skip) is applied by block i + 1's expand conv while it loads its rows
         # (training passes; inference keeps the stand-alone apply)
-        ex_ = [b for b in a.blocks if b.executed]
+        ex_ = a.executed()
         self.bn2_deferred = [bool(L.fuse_bn2 and i + 1 < len(ex_) and ex_[i + 1].expand != 1 and act_dtype in (torch.float32, torch.bfloat16) and
                                   ops.conv2d_fwd_bnin_ok(N, ex_[i].h_out, ex_[i].h_out, ex_[i].cout, ex_[i + 1].cexp)) for i in range(len(ex_))]
         self.stats_part3 = buf(max([-(-(N * b.h_out ** 2) // 16) * 2 * b.cout for b, d in zip(ex_, self.bn2_deferred) if d] + [0]) + 64)
         # the squeeze-excite backward and the depthwise batch norm's backward share ONE pass over (da2, z1) (ops.se_bn_bwd_sums): its
         # per-image chunk sums, and the batch norm's stage-1 sums per image that ops.se_mlp_bwd_bn forms from them
-        self.sums_part = buf(max([ops.se_bn_bwd_sums_floats(N, b.h_out * b.h_out, b.cexp) for b in a.blocks if b.executed] + [0]) + 64)
-        self.stage1_se = buf(max([2 * N * b.cexp for b in a.blocks if b.executed] + [0]) + 64)
+        self.sums_part = buf(max([ops.se_bn_bwd_sums_floats(N, b.h_out * b.h_out, b.cexp) for b in a.executed()] + [0]) + 64)
+        self.stage1_se = buf(max([2 * N * b.cexp for b in a.executed()] + [0]) + 64)
         # squeeze-excite pooling partials of the bn1 apply pass: [N][ceil(rows_per_img / 128)][C]
-        self.pool_part = buf(max(N * (-(-(b.h_out * b.h_out) // 128)) * b.cexp for b in a.blocks if b.executed) + 64)
+        self.pool_part = buf(max(N * (-(-(b.h_out * b.h_out) // 128)) * b.cexp for b in a.executed()) + 64)
         # gate-gradient partials of the project backward-data launch on the small maps: [16-row groups][2][C]
-        self.gate_part = buf(max([(-(-(N * b.h_out * b.h_out) // 16)) * 2 * b.cexp for b in a.blocks if b.executed and 16 <= b.h_out * b.h_out <= 256]
+        self.gate_part = buf(max([(-(-(N * b.h_out * b.h_out) // 16)) * 2 * b.cexp for b in a.executed() if 16 <= b.h_out * b.h_out <= 256]
                                  + [0]) + 64)
         # ---- deferred weight-gradient folds: every *_bwd_filter leaves its per-split slabs in a region of fold_buf and ONE
         #      mliis_fold_batched launch at the end of the backward pass reduces them all into the gradient arena
@@ -182,7 +180,7 @@ class _Plan:
             tile += -(-total // fold_tile)
         fe = a.name
         add(f"{fe}/stem/conv2d/kernel", lib.size("mliis_stem_conv_bwd_filter_workspace_floats", N, H, H, a.stem_out), 27 * a.stem_out)
-        for b, nm, B in zip([b for b in a.blocks if b.executed], L.n_blocks, self.blocks):
+        for b, nm, B in zip(a.executed(), L.n_blocks, self.blocks):
             ce = b.cexp
             if b.expand != 1:
                 add(nm["w_exp"], lib.size("mliis_conv2d_bwd_filter_workspace_floats", N, b.h_in, b.h_in, b.cin, ce, 1), b.cin * ce)
@@ -226,7 +224,7 @@ class _Plan:
                 seg=(2 * co * co, m.c_pyr * co, 0))
         # squeeze-excite weight gradients of all blocks: one launch (descriptor table of device addresses)
         rows_se, se_tile = [], 0
-        for b, B, nm in zip([b for b in a.blocks if b.executed], self.blocks, L.n_blocks):
+        for b, B, nm in zip(a.executed(), self.blocks, L.n_blocks):
             se = nm["se"]
             rows_se.append([B["s"].data_ptr(), B["hpre"].data_ptr(), B["dpre1"].data_ptr(), B["dpre2"].data_ptr()] +
                            [A.g[k].data_ptr() for k in se] + [N, b.cexp, b.se, se_tile])

@@ -152,6 +152,10 @@ class Arch:
     skipdec: Optional[SkipDec] = None   # --skip_decoding: between the (ASPP'd) embedded image and the RSD modules
     c_final: int = 0                # channels of the decoded map the final 1x1 conv reads
 
+    def executed(self) -> List[Block]:
+        """The blocks the model runs, in order (those behind the deepest endpoint the decoder reads are built, never executed)."""
+        return [b for b in self.blocks if b.executed]
+
 
 ASPP_DILATION = 6        # models/efficientlab.py:265-267 (96 / downsample factor 16)
 ASPP_DROPOUT = 0.5       # models/efficientlab.py:248
