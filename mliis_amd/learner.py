@@ -571,13 +571,14 @@ class Learner(_Passes):
 
     # ------------------------------------------------------------------------------------------- inference
     def predict(self, images, training: bool = False, return_logits: bool = False):
-        """predictions tensor of the reference: (softmax(logits) > 0.5) as float, [N,H,W,2]."""
+        """predictions tensor of the reference: (softmax(logits) > 0.5) as float, [N,H,W,2].  training=True: batch statistics in every
+        batch norm; the stochastic sites (drop-connect, final-layer and ASPP dropout) stay off -- their masks belong to a training step."""
         images = torch.as_tensor(images)
         N = images.shape[0]
         P = self._plan(N, infer=True)
         with torch.cuda.stream(self.stream):
             x = images.to(device=self.device, dtype=torch.float32).contiguous()
-            logits = self._forward(P, x, None, training)
+            logits = self._forward(P, x, None, training, stochastic=False)
             dummy = torch.zeros_like(logits)
             ops.softmax_ce(logits, dummy, None, 0.0, False, 0.0, want_grad=False, want_pred=True, pred=P.pred, out=P.loss_out, ws=self.ws)
             out = P.pred.clone()

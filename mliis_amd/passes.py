@@ -18,8 +18,9 @@ from .plan import _Plan
 class _Pass:
     """One pass over a plan: the learner, the plan, the mode, and the launches every stage shares."""
 
-    def __init__(self, L, P: _Plan, training: bool):
+    def __init__(self, L, P: _Plan, training: bool, stochastic: bool = True):
         self.L, self.P, self.training = L, P, training
+        self.stochastic = training and stochastic   # drop-connect / dropout masks are applied (a training step; predict() never)
         self.w, self.mv, self.g, self.ws = L.arena.w, L.arena.mv, L.arena.g, L.ws
 
     def moving(self, prefix):
@@ -135,8 +136,10 @@ class _Passes:
         return self.x3 is not None and self.x3.has(wname, "fwd") and xin.shape[0] * xin.shape[1] * xin.shape[2] >= self.X3_MIN_ROWS
 
     # ------------------------------------------------------------------------------------------- forward
-    def _forward(self, P: _Plan, x, idx, training: bool, upsample: bool = True):
-        a, S = self.arch, _Pass(self, P, training)
+    def _forward(self, P: _Plan, x, idx, training: bool, upsample: bool = True, stochastic: bool = True):
+        """stochastic=False (predict): training mode means batch statistics only -- no drop-connect scale and no dropout mask is read,
+        so the plan's mask buffers (never written outside a training step) stay out of the result."""
+        a, S = self.arch, _Pass(self, P, training, stochastic)
         # (the weight shadows of the step and -- in a training step that draws its masks on the device -- the masks: ONE launch)
         ops.transpose_weights(self.arena.theta, self.theta_t, self.wt_desc, self.w_amax, tiles=self.wt_tiles, x3=self.x3, rng=self._rng_now)
         self._rng_now = None
@@ -155,12 +158,12 @@ class _Passes:
         ends = {r: P.blocks[bi]["out"] for r, bi in a.reductions.items() if bi < len(P.blocks)}
         dec = ends[4]
         if a.aspp:
-            dec = self._aspp_forward(P, dec, training)
+            dec = self._aspp_forward(P, dec, S.stochastic)
         if a.skipdec is not None:
             dec = self._skipdec_fwd(S, dec, ends)
         for j in range(len(a.rsd)):
             dec = self._rsd_fwd(S, j, dec, ends)
-        mask = P.drop_mask if (training and P.drop_mask is not None) else None
+        mask = P.drop_mask if (S.stochastic and P.drop_mask is not None) else None
         P.dec_in = dec
         ops.final_conv_fwd(dec, S.w[self.n_final[0]], S.w[self.n_final[1]], mask, out=P.small)
         H = a.image_size
@@ -251,7 +254,7 @@ class _Passes:
         defer = S.training and P.bn2_deferred[bi]
         # squeeze-excite gate applied inside the project GEMM's A loader (the gated tensor is never written)
         nb = S.conv(B["a1"], nm["w_proj"], None, 1, B["z2"], False, x_scale=B["gate"], part=P.stats_part3 if defer else None)
-        use_dc = B["use_dc"] = S.training and self.drop_connect and b.skip and b.drop_rate > 0
+        use_dc = B["use_dc"] = S.stochastic and self.drop_connect and b.skip and b.drop_rate > 0
         img_scale, res = (B["dc"] if use_dc else None), (B["x_in"] if b.skip else None)
         if defer:
             if nb == 0:
@@ -324,14 +327,14 @@ class _Passes:
         return S.bn(D["zf"], D["stf"], nf, D["out"], pre=True, res=res_up, fused=True, nblk=nb)
 
     # ------------------------------------------------------------------------------------------- ASPP (--spatial_pyramid_pooling)
-    def _aspp_forward(self, P: _Plan, x, training: bool):
+    def _aspp_forward(self, P: _Plan, x, dropout: bool):
         """models/efficientlab.py:248-289 on the encoder output x [N,h,h,Cin]: 1x1 / 3x3-dilation-6 / image-pooling branches written
         straight into channel slices of the concat buffer ([pooled | 3x3 | 1x1], the reference's order), then 1x1 conv + swish +
         dropout.  The dense convs are the MFMA implicit GEMM, the activations mliis_swish_mask_*."""
         a, w, ws, T, N = self.arch, self.arena.w, self.ws, P.aspp, P.N
         d, hw = a.aspp_dimension, a.aspp_h * a.aspp_h
         (k0, c0), (k1, c1), (k2, c2), (ko, co) = self.n_aspp
-        m = T["masks"] if training else [None] * 4
+        m = T["masks"] if dropout else [None] * 4
         cat = T["cat"]
         self._conv_fwd(x, w[k0], w[c0], 1, out=T["z0"], ws=ws, wt=self.wt[k0], fp8_w_amax=self._amax_of.get(k0))
         ops.swish_mask_fwd(T["z0"], m[0], out=cat[..., 2 * d:])
@@ -344,7 +347,7 @@ class _Passes:
         ops.chan_affine(None, A=T["b2"], out=cat[..., :d])      # bilinear resize of the 1x1 pooled map = broadcast
         self._conv_fwd(cat, w[ko], w[co], 1, out=T["zo"], ws=ws, wt=self.wt[ko], fp8_w_amax=self._amax_of.get(ko))
         ops.swish_mask_fwd(T["zo"], m[3], out=T["out"])
-        T["trained"] = training
+        T["trained"] = dropout
         return T["out"]
 
     def _aspp_backward(self, P: _Plan, x, dx, dx_has: bool):
