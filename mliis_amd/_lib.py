@@ -121,26 +121,38 @@ SIGNATURES = {
 }
 
 
+# libmliis_score.so (include/mliis_score.h): the evaluation scores, a library of its own beside the training step's
+SCORE_LIB_PATH = os.path.join(_HERE, "libmliis_score.so")
+SCORE_SIGNATURES = {
+    "mliis_score_last_error": (C.c_char_p, []),
+    "mliis_mask_iou_counts": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+}
+
+
 class MliisError(RuntimeError):
     pass
 
 
 class _Lib:
-    def __init__(self):
+    def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
+        """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
+        library of the same conventions (score_lib)."""
         self._dll = None
+        self._path, self._signatures, self._last_error = path, signatures, last_error
 
     def load(self):
         if self._dll is None:
-            if not os.path.exists(LIB_PATH):
+            path, signatures = (self._path or LIB_PATH), (SIGNATURES if self._signatures is None else self._signatures)
+            if not os.path.exists(path):
                 raise MliisError(
-                    "libmliis_hip.so not found at {} -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                    "or `make -C mliis_amd/csrc`.  There is no CPU fallback.".format(LIB_PATH))
+                    "{} not found at {} -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                    "or `make -C mliis_amd/csrc`.  There is no CPU fallback.".format(os.path.basename(path), path))
             # PyTorch-ROCm carries its own HIP runtime: import it FIRST so that this library resolves libamdhip64 to the copy torch
             # has already loaded.  Loaded the other way round, the process ends up with two HIP runtimes and the one this library is
             # bound to sees no device ("no ROCm-capable device is detected" at the first launch).
             import torch  # noqa: F401
-            dll = C.CDLL(LIB_PATH)
-            for name, (res, args) in SIGNATURES.items():
+            dll = C.CDLL(path)
+            for name, (res, args) in signatures.items():
                 fn = getattr(dll, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -158,7 +170,7 @@ class _Lib:
             self.trace.append((name, args))
         rc = getattr(self.load(), name)(*args)
         if rc != 0:
-            msg = self._dll.mliis_last_error()
+            msg = getattr(self._dll, self._last_error)()
             raise MliisError("{} failed ({}): {}".format(name, rc, msg.decode() if msg else "?"))
 
     def size(self, name, *args) -> int:
@@ -166,3 +178,4 @@ class _Lib:
 
 
 lib = _Lib()
+score_lib = _Lib(SCORE_LIB_PATH, SCORE_SIGNATURES, "mliis_score_last_error")

@@ -118,6 +118,9 @@ _EXT = [
                                      "training steps, fp32 statistics / accumulation / weights (BASELINE configs[3])")),
     ("--checkpoint-format", dict(choices=["npz", "tf"], default="npz",
                                  help="tensor container of written checkpoints: numpy .npz or a TensorFlow TensorBundle (.index/.data)")),
+    ("--device-metrics", dict(action="store_true", help="score evaluation images on the device (Learner.score_resident: four pixel counts per image come back instead "
+                                   "of the prediction mask; the same IoUs bit for bit; its speed against the default host path has not been "
+                                   "measured)")),
 ]
 
 
@@ -175,7 +178,7 @@ def train_kwargs(a) -> dict:
                 inner_iters=a.inner_iters, replacement=a.replacement, meta_step_size=a.meta_step, meta_step_size_final=a.meta_step_final,
                 meta_batch_size=a.meta_batch, meta_iters=a.meta_iters, eval_inner_batch_size=a.eval_batch, eval_inner_iters=a.eval_iters,
                 eval_interval=a.eval_interval, weight_decay_rate=a.weight_decay, transductive=a.transductive, meta_fn=_meta_fn(a),
-                aug_rate=a.aug_rate)
+                aug_rate=a.aug_rate, device_metrics=bool(getattr(a, "device_metrics", False)))
 
 
 def evaluate_kwargs(a) -> dict:
@@ -183,7 +186,8 @@ def evaluate_kwargs(a) -> dict:
                 replacement=a.replacement, weight_decay_rate=a.weight_decay, num_samples=a.eval_samples, transductive=a.transductive,
                 meta_fn=_meta_fn(a), augment=augment_mode(a), lr=None, aug_rate=a.aug_rate,
                 eval_tasks_with_median_early_stopping_iterations=a.eval_tasks_with_median_early_stopping_iterations,
-                save_fine_tuned_checkpoints=a.save_fine_tuned_checkpoints, save_fine_tuned_checkpoints_dir=a.save_fine_tuned_checkpoints_dir)
+                save_fine_tuned_checkpoints=a.save_fine_tuned_checkpoints, save_fine_tuned_checkpoints_dir=a.save_fine_tuned_checkpoints_dir,
+                device_metrics=bool(getattr(a, "device_metrics", False)))
 
 
 def hyper_search_kwargs(a) -> dict:

@@ -4,29 +4,9 @@
 // Reference: models/efficientlab.py:161-177 (dropout -> 1x1 -> resize -> softmax -> >0.5), :205-206 (RSD upsample),
 // :294-303,319-327,329-396 (loss).  All HBM-bound, all deterministic (gather-form backward, two-stage reductions).
 #include "common.hpp"
+#include "head_math.hpp"
 
 namespace mliis {
-
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  typedef float4 T;
-};
-template <>
-struct Vec<2> {
-  typedef float2 T;
-};
-__device__ __forceinline__ float4 vfma(float s, float4 a, float4 c) {
-  return make_float4(fmaf(s, a.x, c.x), fmaf(s, a.y, c.y), fmaf(s, a.z, c.z), fmaf(s, a.w, c.w));
-}
-__device__ __forceinline__ float2 vfma(float s, float2 a, float2 c) { return make_float2(fmaf(s, a.x, c.x), fmaf(s, a.y, c.y)); }
-template <class T>
-__device__ __forceinline__ T vzero();
-template <>
-__device__ __forceinline__ float4 vzero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-template <>
-__device__ __forceinline__ float2 vzero<float2>() { return make_float2(0.f, 0.f); }
 
 template <int V>
 __global__ __launch_bounds__(256) void resize_fwd_k(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int N,
@@ -45,20 +25,7 @@ __global__ __launch_bounds__(256) void resize_fwd_k(const float* __restrict__ x,
     float ly, lx;
     src_coord(ho, sh, Hi, y0, y1, ly);
     src_coord(wo, sw, Wi, x0, x1, lx);
-    const float* base = x + (long long)n * Hi * Wi * ldx + c;
-    const T tl = *reinterpret_cast<const T*>(base + ((long long)y0 * Wi + x0) * ldx);
-    const T tr = *reinterpret_cast<const T*>(base + ((long long)y0 * Wi + x1) * ldx);
-    const T bl = *reinterpret_cast<const T*>(base + ((long long)y1 * Wi + x0) * ldx);
-    const T br = *reinterpret_cast<const T*>(base + ((long long)y1 * Wi + x1) * ldx);
-    // top = tl + (tr - tl) * lx ; bottom likewise ; out = top + (bottom - top) * ly   (TF ResizeBilinear form)
-    T o = vzero<T>();
-    float wtl, wtr, wbl, wbr;
-    bilinear_weights(ly, lx, wtl, wtr, wbl, wbr);
-    o = vfma(wtl, tl, o);
-    o = vfma(wtr, tr, o);
-    o = vfma(wbl, bl, o);
-    o = vfma(wbr, br, o);
-    *reinterpret_cast<T*>(y + p * ldy + c) = o;
+    *reinterpret_cast<T*>(y + p * ldy + c) = bilinear_sample<T>(x + (long long)n * Hi * Wi * ldx + c, Wi, ldx, y0, y1, x0, x1, ly, lx);
   }
 }
 
@@ -365,10 +332,8 @@ __global__ __launch_bounds__(256) void ce_grad_k(const float* __restrict__ logit
   for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
     const float2 zz = *reinterpret_cast<const float2*>(z + (long long)p * 2);
     const float2 tt = *reinterpret_cast<const float2*>(t + (long long)p * 2);
-    const float m = fmaxf(zz.x, zz.y);
-    const float e0 = expf(zz.x - m), e1 = expf(zz.y - m);
-    const float inv = 1.f / (e0 + e1);
-    const float p0 = e0 * inv, p1 = e1 * inv;
+    float p0, p1;
+    softmax2(zz, p0, p1);
     const float t0 = tt.x * (1.f - ls) + 0.5f * ls, t1 = tt.y * (1.f - ls) + 0.5f * ls;
     const float ts = t0 + t1;
     float d0 = (p0 * ts - t0) * inv_rows, d1 = (p1 * ts - t1) * inv_rows;

@@ -484,6 +484,25 @@ class Learner(_Passes):
         self._backward(P, self.shots_x, P.idx, head_fused=head_fused)
         self._apply()
 
+    def _upload_idx(self, P: _Plan, idx: Sequence[int]):
+        """A batch's image indices into P.idx through the ring of pinned slots (call on the learner's stream): inner_step's upload, for
+        the callers outside the training step (score_resident).  inner_step keeps its own inline form -- the training step's code is
+        left exactly as it was; the two share the ring (slots, events, counter)."""
+        N = len(idx)
+        if N <= self._idx_pin.shape[1]:
+            slot = self._idx_n % len(self._idx_ev)
+            self._idx_n += 1
+            if self._idx_ev[slot] is not None:
+                self._idx_ev[slot].synchronize()   # the upload that last used this slot (16 uploads ago) has been consumed
+            else:
+                self._idx_ev[slot] = torch.cuda.Event()
+            src = self._idx_pin[slot, :N]
+            src.copy_(torch.tensor(list(idx), dtype=torch.int32))
+            ops.copy_words(src, P.idx)   # one small kernel reading the pinned slot: no copy engine between two steps
+            self._idx_ev[slot].record(self.stream)
+        else:
+            P.idx.copy_(torch.tensor(list(idx), dtype=torch.int32), non_blocking=True)
+
     def inner_step(self, batch_idx: Sequence[int], lr: Optional[float] = None, dc_scales: Optional[Dict[int, torch.Tensor]] = None,
                    dropout_mask: Optional[torch.Tensor] = None, weight_decay_rate: float = 1.0, drop_rate: Optional[float] = None,
                    aspp_masks: Optional[Sequence[torch.Tensor]] = None):
@@ -591,6 +610,31 @@ class Learner(_Passes):
         with torch.cuda.stream(self.stream):
             x = self.shots_x[torch.tensor(list(idx), dtype=torch.long, device=self.device)]
         return self.predict(x, training=training)
+
+    def score_resident(self, idx: Sequence[int], training: bool = False) -> np.ndarray:
+        """The score of predict_resident(idx) against the resident labels without its mask: int64 [len(idx), 4] =
+        {|P & L|, |P | L|, |P|, |L|} per image (ops.mask_iou_counts; metrics.iou_from_counts(row[0], row[1]) is metrics.iou of that
+        image's prediction).  The images are read through the index vector and the decoder-resolution logits are scored in place: no
+        gather, no resize launch, no full-resolution tensor, 16 bytes per image back to the host."""
+        idx = [int(i) for i in idx]
+        N = len(idx)
+        if N == 0:
+            raise ValueError("empty batch")
+        lim = self.max_shots + self._aug_valid if self._aug_valid else self.n_shots
+        if min(idx) < 0 or max(idx) >= lim or any(self.n_shots <= i < self.max_shots for i in idx):
+            raise ValueError("image index out of range of the resident task ({} shots)".format(self.n_shots))
+        P = self._plan(N, infer=True)
+        H = self.arch.image_size
+        with torch.cuda.stream(self.stream):
+            if P.counts is None:
+                P.counts = torch.zeros((N, 4), dtype=torch.int32, device=self.device)
+                P.counts_pin = torch.zeros((N, 4), dtype=torch.int32).pin_memory()
+            self._upload_idx(P, idx)
+            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            ops.mask_iou_counts(P.small, self.shots_y, P.idx, (H, H), counts=P.counts)
+            P.counts_pin.copy_(P.counts, non_blocking=True)
+        self.stream.synchronize()
+        return P.counts_pin.numpy().astype(np.int64)
 
     def close(self):
         """Destroy the captured HIP graphs (the buffers themselves are torch tensors and go with the object)."""

@@ -22,6 +22,12 @@ def iou(prediction: np.ndarray, label: np.ndarray, epsilon: float = 1e-7, class_
     return (np.count_nonzero(p & l) + epsilon) / (np.count_nonzero(p | l) + epsilon)
 
 
+def iou_from_counts(intersection, union, epsilon: float = 1e-7) -> float:
+    """iou() from the two pixel counts it ends in (ops.mask_iou_counts: counts[n][0], counts[n][1]): the same float64 expression, so
+    the two agree to the last bit."""
+    return (int(intersection) + epsilon) / (int(union) + epsilon)
+
+
 def measure(y_in, pred_in, thresh: float = 0.5):
     y, p = np.asarray(y_in) > thresh, np.asarray(pred_in) > thresh
     return (int((y & p).sum()), int((~y & ~p).sum()), int((~y & p).sum()), int((y & ~p).sum()))

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import MliisError, lib
+from ._lib import MliisError, lib, score_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1233,6 +1233,29 @@ def head_ce_fused(small, labels, idx, size, label_smoothing, dsmall, out, extra_
                                                  float(label_smoothing), float(extra_loss), _ptr(dsmall), _ptr(out) if finalize else None, _ptr(buf),
                                                  buf.numel(), _stream()))
     return (out, dsmall) if finalize else (out, dsmall, buf)
+
+
+def mask_iou_counts(small, labels, idx, size, counts=None):
+    """counts [N,4] int32 = {|P & L|, |P | L|, |P|, |L|} per image: P = the channel-1 prediction mask of resize(small -> size) -> softmax
+    > 0.5 (the mask resize_bilinear_fwd -> softmax_ce(want_pred=True) writes, bit for bit), L = round(label channel 1) != 0 of labels
+    [S,H,W,2] through idx (nullable).  Neither the full-resolution logits nor the mask are written (metrics.iou_from_counts scores).
+    The one entry point of libmliis_score.so (include/mliis_score.h, csrc/score.hip)."""
+    N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx, counts)
+    H, W = int(size[0]), int(size[1])
+    if small.shape[-1] != 2 or labels.dim() != 4 or tuple(labels.shape[1:]) != (H, W, 2):
+        raise MliisError("mask_iou_counts: expected small [N,Hd,Wd,2] and labels [S,{},{},2], got {} / {}".format(H, W, tuple(small.shape),
+                                                                                                            tuple(labels.shape)))
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != N):
+        raise MliisError("mask_iou_counts: idx must hold {} int32 image indices".format(N))
+    if idx is None and labels.shape[0] < N:
+        raise MliisError("mask_iou_counts: {} label images for {} predictions".format(labels.shape[0], N))
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (N, 4) or not counts.is_cuda):
+        raise MliisError("mask_iou_counts counts: expected a device int32 tensor of shape {}, got {} {}".format((N, 4), tuple(counts.shape), counts.dtype))
+    counts = torch.empty((N, 4), dtype=torch.int32, device=small.device) if counts is None else counts
+    _timed("mask_iou_counts", {}, lambda: score_lib.call("mliis_mask_iou_counts", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd, H, W,
+                                                   C.c_void_p(counts.data_ptr()), _stream()))
+    return counts
 
 
 def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None):

@@ -126,6 +126,8 @@ class _Plan:
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
         # the fused head launch's workspace (the first step that takes it allocates it) and its hand-over to the final conv's backward-data
         self.head_ws = self.head_fin = None
+        # Learner.score_resident: the [N,4] IoU counts on the device and their pinned host copy (allocated by the first scoring call)
+        self.counts = self.counts_pin = None
         # stage-1 BN statistics handed from a producer (GEMM epilogue / stats kernel) to the fused fold+apply kernel
         need = 0
         for b in a.executed():

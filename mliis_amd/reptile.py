@@ -122,8 +122,13 @@ class Gecko:
 
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
-                 aug_pool=None, lanes: Sequence = ()):
+                 aug_pool=None, lanes: Sequence = (), device_metrics: bool = False):
         self.learner = learner
+        # device_metrics: the evaluation sites score on the device (Learner.score_resident: four integers per image come back) instead of
+        # copying every prediction mask to the host for metrics.iou; the same IoUs, bit for bit.  Opt-in; the default path is untouched.
+        self.device_metrics = bool(device_metrics)
+        if self.device_metrics and not all(callable(getattr(ln, "score_resident", None)) for ln in [learner] + list(lanes)):
+            raise ValueError("device_metrics=True needs a learner with score_resident() (the device Learner; the CPU oracle has none)")
         # lanes: further Learners of the same architecture (own arenas, own streams).  The tasks of a meta-batch that fall on this
         # rank are then adapted len(lanes)+1 at a time, their inner steps issued round-robin so the launches of one task fill the
         # compute units the other leaves idle (one 8-image step alone does not fill 256 CUs: profiles/r01_notes.md).  Same update as
@@ -424,9 +429,12 @@ class Gecko:
                     if j < len(schedule):
                         self._fine_tune_step([train_idx[i] for i in schedule[j]], j, lr, self.lr_scheduler, drop_rate, lane)
             for lane, name, _, labels, train_idx, test_idx, _ in group:
-                preds = self._test_predictions(train_idx, test_idx, lane)
-                lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
-                class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
+                if self.device_metrics:
+                    class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane)))
+                else:
+                    preds = self._test_predictions(train_idx, test_idx, lane)
+                    lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+                    class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
                 print("Mean task IoU: {}".format(class_iou))
                 out.append((name, class_iou))
             L.import_all(state)
@@ -482,9 +490,12 @@ class Gecko:
             save_fine_tuned_checkpoint(L.named_numpy(), save_fine_tuned_checkpoints_dir, task_name, eval_sample_num, inner_iter)
         if self.augmenter is not None and not self.device_aug:
             L.load_task(images, labels)   # the augmented batches replaced the resident task
-        preds = self._test_predictions(train_idx, test_idx)
-        lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
-        class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
+        if self.device_metrics:
+            class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx)))
+        else:
+            preds = self._test_predictions(train_idx, test_idx)
+            lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+            class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
         print("Mean task IoU: {}".format(class_iou))
         L.import_all(old)
         return class_iou
@@ -531,8 +542,11 @@ class Gecko:
             self._fine_tune_step(idx, inner_iter, lr, lr_scheduler, drop_rate)
             if self.augmenter is not None and not self.device_aug:
                 L.load_task(images, labels)   # predictions read the ORIGINAL examples
-            preds = self._test_predictions(train_idx, val_idx)
-            miou = np.nanmean([_iou(preds[j], lab[val_idx[j]]) for j in range(len(val_idx))])
+            if self.device_metrics:
+                miou = np.nanmean(self._device_ious(train_idx, val_idx))
+            else:
+                preds = self._test_predictions(train_idx, val_idx)
+                miou = np.nanmean([_iou(preds[j], lab[val_idx[j]]) for j in range(len(val_idx))])
             if not stopper.continue_training(miou, inner_iter + 1):
                 break
         best_num_steps, best_iou = stopper.best_num_steps(), stopper.best_metric()
@@ -640,6 +654,18 @@ class Gecko:
         for t in test_idx:
             out.append(L.predict_resident(list(train_idx) + [t], training=False)[-1].cpu().numpy())
         return out
+
+    def _device_ious(self, train_idx, test_idx, L=None) -> List[float]:
+        """device_metrics: the per-image IoUs of _test_predictions + metrics.iou from the device's counts, over the same batches --
+        transductive: one batch of all test images; otherwise one batch [train images..., that test image] per test image, its last
+        row kept."""
+        from .metrics import iou_from_counts
+        L = L or self.learner
+        if self._transductive:
+            rows = L.score_resident(list(test_idx), training=False)
+        else:
+            rows = [L.score_resident(list(train_idx) + [t], training=False)[-1] for t in test_idx]
+        return [iou_from_counts(r[0], r[1]) for r in rows]
 
 
 class FOMLIS(Gecko):

@@ -13,6 +13,8 @@ early-stopping harness of the reference + a built-in GP / expected-improvement o
 (mliis_amd/augment.py); the pixel work runs on the device (csrc/augment.hip), or in numpy / scipy on the host with --augment-on-host
 (draw-identical noise fields too).  Checkpoints: numpy .npz or TensorFlow TensorBundle files (--checkpoint-format tf; restoring takes either).  Data: --data-dir with FSS-1000 TFRecord-GZIP shards
 (mliis_amd/tfrecord.py, no TensorFlow needed) or --synthetic-tasks N.
+--device-metrics: every evaluation (the periodic ones of meta-training, the final passes, the update-hyperparameter search, the k-shot
+curves) scores on the device -- four pixel counts per test image come back instead of its prediction mask; the same IoUs bit for bit.
 """
 import datetime
 import json
