@@ -391,91 +391,7 @@ static inline bool stream_plan(long long M, int K, int Nout, int num_cus, Stream
   sp->gx = (int)gx;
   return true;
 }
-template <bool AIN>
-static bool launch_stream_f32(const StreamPlan& sp, const ConvGemmParams& p, hipStream_t stream) {
-  dim3 grid(sp.gx, sp.gy), block(64 * kStreamWaves);
-#define S(KC_, NT_) hipLaunchKernelGGL((conv1x1_stream_k<KC_, NT_, 0, AIN>), grid, block, 0, stream, p, sp.row_groups); break;
-#define SN(KC_, NT_) if constexpr (AIN) return false; else { S(KC_, NT_) }   // (stream_plan gives at most four column tiles: no AIN instance)
-  switch (sp.kc) {
-    case 1: switch (sp.nt) { case 1: S(1, 1) case 2: S(1, 2) case 3: S(1, 3) case 4: S(1, 4) case 5: SN(1, 5) case 6: SN(1, 6) case 7: SN(1, 7) case 8: SN(1, 8) default: return false; } break;
-    case 2: switch (sp.nt) { case 1: S(2, 1) case 2: S(2, 2) case 3: S(2, 3) case 4: S(2, 4) default: return false; } break;
-    case 3: switch (sp.nt) { case 1: S(3, 1) case 2: S(3, 2) default: return false; } break;
-    case 4: switch (sp.nt) { case 1: S(4, 1) case 2: S(4, 2) default: return false; } break;
-    case 5: switch (sp.nt) { case 1: S(5, 1) default: return false; } break;
-    case 6: switch (sp.nt) { case 1: S(6, 1) default: return false; } break;
-    case 7: switch (sp.nt) { case 1: S(7, 1) default: return false; } break;
-    default: return false;
-  }
-#undef SN
-#undef S
-  return true;
-}
-static bool launch_stream(const StreamPlan& sp, const ConvGemmParams& p, hipStream_t stream, int precision = MLIIS_PREC_FP32, bool ain = false) {
-  if (precision != MLIIS_PREC_FP32) return launch_stream_lowp(precision, sp.kc, sp.nt, dim3(sp.gx, sp.gy), p, sp.row_groups, stream, ain);
-  return ain ? launch_stream_f32<true>(sp, p, stream) : launch_stream_f32<false>(sp, p, stream);
-}
 
-static int g_num_cus = 0;
-static int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      g_num_cus = prop.multiProcessorCount;
-    else
-      g_num_cus = 256;
-  }
-  return g_num_cus;
-}
-
-static int conv_check(const char* name, int Nimg, int H, int W, int Cin, int Cout, int ksize, int dil) {
-  MLIIS_REQUIRE(Nimg > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, MLIIS_ERR_ARG, "%s: bad shape", name);
-  MLIIS_REQUIRE((Cin & 3) == 0 && (Cout & 3) == 0, MLIIS_ERR_ARG, "%s: channel counts must be multiples of 4 (Cin=%d Cout=%d)", name,
-                Cin, Cout);
-  MLIIS_REQUIRE(ksize == 1 || ksize == 3, MLIIS_ERR_UNSUPPORTED, "%s: kernel size %d unsupported (1 or 3)", name, ksize);
-  MLIIS_REQUIRE(dil >= 1, MLIIS_ERR_ARG, "%s: dilation must be >= 1", name);
-  return MLIIS_OK;
-}
-
-}  // namespace mliis
-
-using namespace mliis;
-
-extern "C" {
-
-// Workgroups of a 1x1 kernel instance that fit one CU according to the runtime (profiling aid: the planners assume two 512-thread
-// workgroups per CU -- a register count above 128 silently halves that and the grid runs in two rounds).  kind 0: conv1x1_stream_k<kc, nt>,
-// 1: conv1x1_ksplit_k<kc, nt, 8>; fp32 instances.  Returns MLIIS_ERR_ARG for a combination that is not instantiated.
-int mliis_conv1x1_occupancy(int kind, int kc, int nt, int* blocks_per_cu) {
-  MLIIS_REQUIRE(blocks_per_cu, MLIIS_ERR_ARG, "conv1x1_occupancy: null pointer");
-  const void* fn = nullptr;
-#define ST(KC_, NT_) if (kind == 0 && kc == KC_ && nt == NT_) fn = reinterpret_cast<const void*>(&conv1x1_stream_k<KC_, NT_, 0>);
-#define KS(KC_, NT_) if (kind == 1 && kc == KC_ && nt == NT_) fn = reinterpret_cast<const void*>(&conv1x1_ksplit_k<KC_, NT_, 8, 0>);
-  ST(1, 1) ST(1, 2) ST(1, 3) ST(1, 4) ST(2, 1) ST(2, 2) ST(2, 3) ST(3, 1) ST(3, 2) ST(4, 1) ST(4, 2) ST(5, 1) ST(6, 1) ST(7, 1)
-  KS(1, 1) KS(1, 2) KS(1, 3) KS(1, 4) KS(1, 5) KS(1, 6) KS(1, 7) KS(2, 1) KS(2, 2) KS(2, 3) KS(2, 4) KS(3, 1) KS(3, 2) KS(4, 1) KS(4, 2)
-  KS(5, 1) KS(6, 1) KS(7, 1) KS(4, 3) KS(5, 2) KS(6, 2)
-#undef ST
-#undef KS
-  MLIIS_REQUIRE(fn != nullptr, MLIIS_ERR_ARG, "conv1x1_occupancy: no instance kind %d <%d, %d>", kind, kc, nt);
-  int nb = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 512, 0);
-  MLIIS_REQUIRE(e == hipSuccess, MLIIS_ERR_LAUNCH, "conv1x1_occupancy: %s", hipGetErrorString(e));
-  *blocks_per_cu = nb;
-  return MLIIS_OK;
-}
-
-// Tiling the planner picks for a conv2d_fwd / conv2d_bwd_data call (profiling aid: row-tile factor, column tiles, split-K factor).
-int mliis_conv2d_plan(int Nimg, int H, int W, int Cred, int Nout, int ksize, int* tm, int* nt, int* splits) {
-  MLIIS_REQUIRE(tm && nt && splits, MLIIS_ERR_ARG, "conv2d_plan: null pointer");
-  GemmPlan g = plan_gemm((long long)Nimg * H * W, Nout, Cred, ksize * ksize, num_cus(), 1);
-  *tm = g.tm;
-  *nt = g.nt;
-  *splits = g.gz;
-  return MLIIS_OK;
-}
-
-// Name of the kernel instantiation (as rocprofv3 prints it, without the mliis:: prefix and argument list) that a conv2d_fwd /
-// conv2d_bwd_data call with these shapes launches (has_scale: an x_scale operand is given).
 // ------------------------------------------------------------------------------------------------ long-K 1x1 convs on small maps (conv1x1_ksplit_k)
 // K split over the 8 waves of a workgroup instead of over workgroups + a fold launch: the MBConv project convs forward and expand
 // convs backward-data of the 56x56 / 28x28 / 14x14 maps (K = 144..672, 1568..25088 rows at N = 8).
@@ -507,39 +423,206 @@ static inline bool ksplit_plan(long long M, int K, int Nout, int num_cus, Stream
   sp->gx = (int)gx;
   return true;
 }
-static bool launch_ksplit(const StreamPlan& sp, const ConvGemmParams& p_, hipStream_t stream, int precision) {
-  ConvGemmParams p = p_;
-  dim3 grid(sp.gx, sp.gy);
-  if (precision != MLIIS_PREC_FP32) return launch_ksplit_lowp(precision, sp.kc, sp.nt, grid, p, sp.row_groups, stream);
-  return launch_ksplit_t<0>(sp.kc, sp.nt, grid, p, sp.row_groups, stream);
+
+static int g_num_cus = 0;
+static int num_cus() {
+  if (g_num_cus == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+      g_num_cus = prop.multiProcessorCount;
+    else
+      g_num_cus = 256;
+  }
+  return g_num_cus;
 }
 
-int mliis_conv2d_kernel_name(int Nimg, int H, int W, int Cred, int Nout, int ksize, int has_scale, int precision, char* buf, size_t buf_len) {
-  MLIIS_REQUIRE(buf && buf_len >= 64, MLIIS_ERR_ARG, "conv2d_kernel_name: buffer too small");
-  StreamPlan sp;
-  if (ksize == 1 && !has_scale && stream_plan((long long)Nimg * H * W, Cred, Nout, num_cus(), &sp)) {
-    snprintf(buf, buf_len, "conv1x1_stream_k<%d, %d, %d>", sp.kc, sp.nt, precision);   // (a call without accumulate / border bias)
-    return MLIIS_OK;
-  }
-  if (ksize == 1 && (!has_scale || H * W >= 16) && ksplit_plan((long long)Nimg * H * W, Cred, Nout, num_cus(), &sp)) {
-    snprintf(buf, buf_len, "conv1x1_ksplit_k<%d, %d, 8, %d>", sp.kc, sp.nt, precision);
-    return MLIIS_OK;
-  }
-  GemmPlan g = plan_gemm((long long)Nimg * H * W, Nout, Cred, ksize * ksize, num_cus(), 1);
-  if (g.sk_parts > 0 && !has_scale) {   // (+ sk_fixup_k<NT> for the remainder tiles)
-    snprintf(buf, buf_len, "conv_gemm_sk_k<%d, 2, false, %d>", g.nt, precision == MLIIS_PREC_FP8 ? MLIIS_PREC_BF16 : precision);
-    return MLIIS_OK;
-  }
-  snprintf(buf, buf_len, "conv_gemm_nk_k<%d, %d, %d, %s, %s, %s, %d>", g.tm, g.nt, g.tm == 1 ? 2 : 1, has_scale ? "true" : "false",
-           g.gz > 1 ? "true" : "false", gemm_narrow(ksize * ksize, Cred) ? "true" : "false", (precision == MLIIS_PREC_FP8 && ksize != 1) ? MLIIS_PREC_BF16 : precision);
+static int conv_check(const char* name, int Nimg, int H, int W, int Cin, int Cout, int ksize, int dil) {
+  MLIIS_REQUIRE(Nimg > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, MLIIS_ERR_ARG, "%s: bad shape", name);
+  MLIIS_REQUIRE((Cin & 3) == 0 && (Cout & 3) == 0, MLIIS_ERR_ARG, "%s: channel counts must be multiples of 4 (Cin=%d Cout=%d)", name,
+                Cin, Cout);
+  MLIIS_REQUIRE(ksize == 1 || ksize == 3, MLIIS_ERR_UNSUPPORTED, "%s: kernel size %d unsupported (1 or 3)", name, ksize);
+  MLIIS_REQUIRE(dil >= 1, MLIIS_ERR_ARG, "%s: dilation must be >= 1", name);
   return MLIIS_OK;
 }
 
-// Workspace (floats) that conv2d_fwd / conv2d_bwd_data may need for split-K partials.
+// ------------------------------------------------------------------------------------------------ routing
+// A conv2d_fwd / conv2d_bwd_data call as the planners see it: the GEMM C[M, Nout] (+)= A[M, taps x K] B.  Every condition that decides
+// the kernel family reads these facts and nothing else.
+struct ConvCall {
+  long long M, HW;               // rows (N H W), rows per image
+  int K, Nout, ntaps;            // reduction width per tap, output width
+  int lda, ldc;                  // leading dimensions of A and C (elements)
+  bool a_bf16, c_bf16;           // bf16 storage of A / C
+  bool has_scale, has_border_bias, accumulate;
+  bool fwd_stats;                // the forward BN statistics are requested (backward-data's stage-1 sums do not count)
+  bool has_ws;                   // a workspace is given: the GEMM may split K / take the stream-K remainder
+  bool ain;                      // mliis_conv2d_fwd_bnin: only a conv1x1_stream_k<..., AIN = true> instance will do
+};
+// The plain call the planner queries describe: dense leading dimensions, fp32 storage, no accumulate, no border bias, a workspace.
+// The entry points start from it and set what their call adds.
+static ConvCall plain_call(int Nimg, int H, int W, int Cred, int Nout, int ksize, bool has_scale) {
+  ConvCall c{};
+  c.M = (long long)Nimg * H * W;
+  c.HW = (long long)H * W;
+  c.K = c.lda = Cred;
+  c.Nout = c.ldc = Nout;
+  c.ntaps = ksize * ksize;
+  c.has_scale = has_scale;
+  c.has_ws = true;
+  return c;
+}
+
+enum ConvRoute { ROUTE_STREAM, ROUTE_KSPLIT, ROUTE_GEMM };
+struct RoutedConv {
+  ConvRoute route;
+  StreamPlan sp;   // ROUTE_STREAM / ROUTE_KSPLIT only
+  GemmPlan g;      // whatever the route: ConvGemmParams::chunks_per_split, mliis_conv2d_plan and the workspace query take it
+};
+// THE routing decision of the dense convs: the launches (forward, backward-data, forward with the batch norm on load) and the planner
+// queries (kernel name, plan, bnin_ok, workspace) all ask here, and nothing else calls the three planners.
+static RoutedConv route_conv(const ConvCall& c) {
+  RoutedConv r;
+  r.route = ROUTE_GEMM;
+  r.g = plan_gemm(c.M, c.Nout, c.K, c.ntaps, num_cus(), c.has_ws);
+  // the two 1x1 kernels address A and C with 32-bit byte offsets and know no border bias
+  if (c.ntaps != 1 || c.has_border_bias || c.M * c.lda * 4 >= (1LL << 31) || c.M * c.ldc * 4 >= (1LL << 31)) return r;
+  // short-K 1x1 convs (the MBConv expand convs forward, project convs backward-data): barrier-free streaming kernel.  It reads an
+  // fp32 A; the instance follows the call's operand precision (one rounding rule for every matrix-core conv of a reduced-precision step)
+  if (!c.has_scale && !c.accumulate && !c.a_bf16 && stream_plan(c.M, c.K, c.Nout, num_cus(), &r.sp) && stream_instance(r.sp.kc, r.sp.nt, c.ain))
+    r.route = ROUTE_STREAM;
+  // long-K 1x1 convs on small maps (project convs forward with the SE gate on load, expand convs backward-data): K split inside the
+  // workgroup, one launch.  Its finishing threads write fp32; the gate goes through LDS: two images per row group at most.  Forward
+  // statistics of an accumulated output are not a valid call and go to the GEMM route, which refuses them (backward-data's stage-1
+  // sums beside accumulate are valid: ConvGemmParams::bnb_x)
+  else if (!c.c_bf16 && !(c.fwd_stats && c.accumulate) && (!c.has_scale || c.HW >= 16) && ksplit_plan(c.M, c.K, c.Nout, num_cus(), &r.sp) &&
+           ksplit_instance(r.sp.kc, r.sp.nt))
+    r.route = ROUTE_KSPLIT;
+  return r;
+}
+
+// The one launch of a ROUTE_STREAM / ROUTE_KSPLIT call (route_conv has seen to it that the instance exists).
+static int launch_1x1(const char* name, const RoutedConv& r, const ConvGemmParams& p, int precision, bool ain, hipStream_t stream) {
+  const StreamPlan& sp = r.sp;
+  const dim3 grid(sp.gx, sp.gy);
+  bool ok;
+  if (r.route == ROUTE_KSPLIT)
+    ok = precision != MLIIS_PREC_FP32 ? launch_ksplit_lowp(precision, sp.kc, sp.nt, grid, p, sp.row_groups, stream)
+                                      : launch_ksplit_t<0>(sp.kc, sp.nt, grid, p, sp.row_groups, stream);
+  else if (precision != MLIIS_PREC_FP32)
+    ok = launch_stream_lowp(precision, sp.kc, sp.nt, grid, p, sp.row_groups, stream, ain);
+  else
+    ok = ain ? launch_stream_t<0, true>(sp.kc, sp.nt, grid, p, sp.row_groups, stream)
+             : launch_stream_t<0, false>(sp.kc, sp.nt, grid, p, sp.row_groups, stream);
+  MLIIS_REQUIRE(ok, MLIIS_ERR_UNSUPPORTED, "%s: no instance <%d, %d>", name, sp.kc, sp.nt);
+  MLIIS_CHECK_LAUNCH(name);
+  return MLIIS_OK;
+}
+
+// The launches of a ROUTE_GEMM call: conv_gemm_nk_k (with the split-K fold behind it when g.gz > 1; fold_stats: the fold also forms the
+// forward BN statistics, of swish(v) when fold_swish) or the stream-K pair.  p.partial is set here.
+static int launch_gemm_route(const char* name, const GemmPlan& g, ConvGemmParams& p, float* ws, size_t ws_floats, int precision,
+                             float* fold_stats, int fold_swish, hipStream_t stream) {
+  const long long M = (long long)p.Nimg * p.H * p.W;
+  if (g.gz > 1) {
+    size_t need = (size_t)g.gz * M * p.Nout;
+    MLIIS_REQUIRE(need <= ws_floats && aligned16(ws) && (p.ldc & 3) == 0 && aligned16(p.Cmat), MLIIS_ERR_WORKSPACE,
+                  "%s: split-K workspace too small (%zu needed, %zu given) or unaligned output", name, need, ws_floats);
+    p.partial = ws;
+  }
+  float* sk_slab = nullptr;
+  if (g.sk_parts > 0 && p.a_scale == nullptr && ws != nullptr && aligned16(ws) && g.sk_slab_floats() <= ws_floats && (p.ldc & 3) == 0) sk_slab = ws;
+  launch_gemm(g, p, precision, stream, sk_slab);
+  MLIIS_CHECK_LAUNCH(name);
+  if (g.gz == 1) return MLIIS_OK;
+  if (fold_stats != nullptr) {
+    hipLaunchKernelGGL(splitk_reduce_stats_k, dim3((unsigned)((M + kRedRows - 1) / kRedRows), (p.Nout + 31) / 32), dim3(256), 0, stream, ws, g.gz,
+                       (int)M, p.Nout, p.Cmat, p.ldc, p.bias, p.border_bias, p.H, p.W, fold_stats, fold_swish);
+  } else {
+    long long q = M * (p.Nout / 4);
+    int blocks = (int)((q + 255) / 256 > 2048 ? 2048 : (q + 255) / 256);
+    hipLaunchKernelGGL(splitk_reduce_k, dim3(blocks), dim3(256), 0, stream, ws, g.gz, M, p.Nout, p.Cmat, p.ldc, p.bias, p.accumulate,
+                       p.border_bias, p.H, p.W);
+  }
+  const hipError_t e = hipGetLastError();
+  MLIIS_REQUIRE(e == hipSuccess, MLIIS_ERR_LAUNCH, "%s_splitk_reduce%s: launch failed: %s", name, fold_stats != nullptr ? "_stats" : "",
+                hipGetErrorString(e));
+  return MLIIS_OK;
+}
+
+// The storage-type word of an output tensor: MLIIS_DT_BLOCKED(v) above bit 8 (the group-blocked layout [channels / v][N H W][v]),
+// MLIIS_DT_F32 | MLIIS_DT_BF16 below.  blocked_ok: the call's own conditions for a blocked output, `what` names them in the message.
+static int out_dtype(const char* name, int word, int channels, bool blocked_ok, const char* what, int* block, bool* bf16) {
+  *block = (word >> 8) & 0xff;
+  const int dt = word & 0xff;
+  *bf16 = dt == MLIIS_DT_BF16;
+  MLIIS_REQUIRE(*block == 0 || ((*block == 2 || *block == 4) && dt == MLIIS_DT_F32 && channels % *block == 0 && blocked_ok), MLIIS_ERR_ARG,
+                "%s: a group-blocked output takes v = 2 | 4 dividing %s and fp32 storage", name, what);
+  MLIIS_REQUIRE(dt == MLIIS_DT_F32 || *bf16, MLIIS_ERR_ARG, "%s: bad storage type", name);
+  return MLIIS_OK;
+}
+
+}  // namespace mliis
+
+using namespace mliis;
+
+extern "C" {
+
+// Workgroups of a 1x1 kernel instance that fit one CU according to the runtime (profiling aid: the planners assume two 512-thread
+// workgroups per CU -- a register count above 128 silently halves that and the grid runs in two rounds).  kind 0: conv1x1_stream_k<kc, nt>,
+// 1: conv1x1_ksplit_k<kc, nt, 8>; fp32 instances.  Returns MLIIS_ERR_ARG for a combination that is not instantiated.
+int mliis_conv1x1_occupancy(int kind, int kc, int nt, int* blocks_per_cu) {
+  MLIIS_REQUIRE(blocks_per_cu, MLIIS_ERR_ARG, "conv1x1_occupancy: null pointer");
+  const void* fn = nullptr;
+#define ST(KC_, NT_, AIN_) if (kind == 0 && kc == KC_ && nt == NT_) fn = reinterpret_cast<const void*>(&conv1x1_stream_k<KC_, NT_, 0>);
+#define KS(KC_, NT_) if (kind == 1 && kc == KC_ && nt == NT_) fn = reinterpret_cast<const void*>(&conv1x1_ksplit_k<KC_, NT_, 8, 0>);
+  MLIIS_STREAM_INSTANCES(ST)
+  MLIIS_KSPLIT_INSTANCES(KS)
+#undef ST
+#undef KS
+  MLIIS_REQUIRE(fn != nullptr, MLIIS_ERR_ARG, "conv1x1_occupancy: no instance kind %d <%d, %d>", kind, kc, nt);
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 512, 0);
+  MLIIS_REQUIRE(e == hipSuccess, MLIIS_ERR_LAUNCH, "conv1x1_occupancy: %s", hipGetErrorString(e));
+  *blocks_per_cu = nb;
+  return MLIIS_OK;
+}
+
+// Tiling the planner picks for a conv2d_fwd / conv2d_bwd_data call (profiling aid: row-tile factor, column tiles, split-K factor).
+int mliis_conv2d_plan(int Nimg, int H, int W, int Cred, int Nout, int ksize, int* tm, int* nt, int* splits) {
+  MLIIS_REQUIRE(tm && nt && splits, MLIIS_ERR_ARG, "conv2d_plan: null pointer");
+  const GemmPlan g = route_conv(plain_call(Nimg, H, W, Cred, Nout, ksize, false)).g;
+  *tm = g.tm;
+  *nt = g.nt;
+  *splits = g.gz;
+  return MLIIS_OK;
+}
+
+// Name of the kernel instantiation (as rocprofv3 prints it, without the mliis:: prefix and argument list) that a conv2d_fwd /
+// conv2d_bwd_data call with these shapes launches (has_scale: an x_scale operand is given).  It describes a plain call: dense leading
+// dimensions, fp32 storage, no accumulate, no border bias, a workspace given.
+int mliis_conv2d_kernel_name(int Nimg, int H, int W, int Cred, int Nout, int ksize, int has_scale, int precision, char* buf, size_t buf_len) {
+  MLIIS_REQUIRE(buf && buf_len >= 64, MLIIS_ERR_ARG, "conv2d_kernel_name: buffer too small");
+  const RoutedConv r = route_conv(plain_call(Nimg, H, W, Cred, Nout, ksize, has_scale != 0));
+  const GemmPlan& g = r.g;
+  if (r.route == ROUTE_STREAM)
+    snprintf(buf, buf_len, "conv1x1_stream_k<%d, %d, %d>", r.sp.kc, r.sp.nt, precision);
+  else if (r.route == ROUTE_KSPLIT)
+    snprintf(buf, buf_len, "conv1x1_ksplit_k<%d, %d, 8, %d>", r.sp.kc, r.sp.nt, precision);
+  else if (g.sk_parts > 0 && !has_scale)   // (+ sk_fixup_k<NT> for the remainder tiles)
+    snprintf(buf, buf_len, "conv_gemm_sk_k<%d, 2, false, %d>", g.nt, precision == MLIIS_PREC_FP8 ? MLIIS_PREC_BF16 : precision);
+  else
+    snprintf(buf, buf_len, "conv_gemm_nk_k<%d, %d, %d, %s, %s, %s, %d>", g.tm, g.nt, g.tm == 1 ? 2 : 1, has_scale ? "true" : "false",
+             g.gz > 1 ? "true" : "false", gemm_narrow(ksize * ksize, Cred) ? "true" : "false", (precision == MLIIS_PREC_FP8 && ksize != 1) ? MLIIS_PREC_BF16 : precision);
+  return MLIIS_OK;
+}
+
+// Workspace (floats) that conv2d_fwd / conv2d_bwd_data may need for split-K partials: the GEMM plan's need whatever the route -- the
+// query cannot know accumulate or a border bias (which send a 1x1 shape to the GEMM), and its value sizes the Workspace a captured
+// graph has baked in, so it must not depend on them.
 size_t mliis_conv2d_workspace_floats(int Nimg, int H, int W, int Cred, int Nout, int ksize) {
-  long long M = (long long)Nimg * H * W;
-  const GemmPlan g = plan_gemm(M, Nout, Cred, ksize * ksize, num_cus(), 1);
-  return g.gz > 1 ? (size_t)g.gz * M * Nout : g.sk_slab_floats();
+  const GemmPlan g = route_conv(plain_call(Nimg, H, W, Cred, Nout, ksize, false)).g;
+  return g.gz > 1 ? (size_t)g.gz * ((long long)Nimg * H * W) * Nout : g.sk_slab_floats();
 }
 
 // y[M, Cout] (ld = ldy) (+)= conv(x[M, Cin] (ld = ldx), w) + bias ; stride 1, TF-SAME, dilation dil; the weights come as the
@@ -554,12 +637,11 @@ int mliis_conv2d_fwd(const float* x, int ldx, const float* x_scale, const float*
   if ((rc = prec_check("conv2d_fwd", precision))) return rc;
   // bf16 STORAGE of x and / or y (an expanded MBConv tensor): bf16 operands on the matrix cores, a 1x1 conv, no accumulate, and no
   // plan that finishes its tiles in a second launch (split-K / stream-K slabs) -- the statistics are formed from the rounded output
-  const int y_block = (y_dtype >> 8) & 0xff;   // MLIIS_DT_BLOCKED(v): y in the group-blocked layout [Cout / v][N H W][v]
-  y_dtype &= 0xff;
-  MLIIS_REQUIRE(y_block == 0 || ((y_block == 2 || y_block == 4) && y_dtype == MLIIS_DT_F32 && Cout % y_block == 0), MLIIS_ERR_ARG,
-                "conv2d_fwd: a group-blocked output takes v = 2 | 4 dividing Cout and fp32 storage");
-  const bool xbf = x_dtype == MLIIS_DT_BF16, ybf = y_dtype == MLIIS_DT_BF16;
-  MLIIS_REQUIRE((x_dtype == MLIIS_DT_F32 || xbf) && (y_dtype == MLIIS_DT_F32 || ybf), MLIIS_ERR_ARG, "conv2d_fwd: bad storage type");
+  int y_block;   // MLIIS_DT_BLOCKED(v): y in the group-blocked layout [Cout / v][N H W][v]
+  bool ybf;
+  if ((rc = out_dtype("conv2d_fwd", y_dtype, Cout, true, "Cout", &y_block, &ybf))) return rc;
+  const bool xbf = x_dtype == MLIIS_DT_BF16;
+  MLIIS_REQUIRE(x_dtype == MLIIS_DT_F32 || xbf, MLIIS_ERR_ARG, "conv2d_fwd: bad storage type");
   if (xbf || ybf) {
     MLIIS_REQUIRE(precision == MLIIS_PREC_BF16 && ksize == 1 && border_bias == nullptr && !(ybf && accumulate), MLIIS_ERR_UNSUPPORTED,
                   "conv2d_fwd: bf16 tensors need MLIIS_PREC_BF16, a 1x1 conv and (bf16 output) no accumulate");
@@ -573,7 +655,17 @@ int mliis_conv2d_fwd(const float* x, int ldx, const float* x_scale, const float*
   long long M = (long long)Nimg * H * W;
   MLIIS_REQUIRE(M * ldx * 4 < (1LL << 31) && (long long)ksize * ksize * Cin_total * Cout * 4 < (1LL << 31), MLIIS_ERR_UNSUPPORTED,
                 "conv2d_fwd: operand larger than 2 GiB (32-bit buffer offsets)");
-  GemmPlan g = plan_gemm(M, Cout, Cin, ksize * ksize, num_cus(), ws != nullptr);
+  ConvCall c = plain_call(Nimg, H, W, Cin, Cout, ksize, x_scale != nullptr);
+  c.lda = ldx;
+  c.ldc = ldy;
+  c.a_bf16 = xbf;
+  c.c_bf16 = ybf;
+  c.has_border_bias = border_bias != nullptr;
+  c.accumulate = accumulate != 0;
+  c.fwd_stats = stats_part != nullptr;
+  c.has_ws = ws != nullptr;
+  const RoutedConv r = route_conv(c);
+  const GemmPlan& g = r.g;
   MLIIS_REQUIRE(ci_begin >= 0 && (ci_begin & 3) == 0 && ci_begin + Cin <= Cin_total, MLIIS_ERR_ARG,
                 "conv2d_fwd: input-channel window out of range");
   MLIIS_REQUIRE(border_bias == nullptr || (ksize == 3 && dil == 1 && H >= 2 && W >= 2 && aligned16(border_bias)), MLIIS_ERR_ARG,
@@ -589,38 +681,16 @@ int mliis_conv2d_fwd(const float* x, int ldx, const float* x_scale, const float*
   MLIIS_REQUIRE(aligned16(x_scale) && (x_scale == nullptr || ksize == 1), MLIIS_ERR_ARG,
                 "conv2d_fwd: x_scale must be 16-byte aligned and is only supported for 1x1 convs");
   if (stats_nblk) *stats_nblk = 0;
-  {  // short-K 1x1 convs (the MBConv expand convs): barrier-free streaming kernel
-    StreamPlan sp;
-    // (the instance follows the call's operand precision: one rounding rule for every matrix-core conv of a reduced-precision step)
-    if (ksize == 1 && x_scale == nullptr && border_bias == nullptr && !accumulate && !xbf && M * ldx * 4 < (1LL << 31) &&
-        M * ldy * 4 < (1LL << 31) && stream_plan(M, Cin, Cout, num_cus(), &sp)) {   // (the streaming kernel reads an fp32 A)
-      MLIIS_REQUIRE(stats_part == nullptr || stats_nblk, MLIIS_ERR_ARG, "conv2d_fwd: fused statistics need a stats_nblk output");
-      p.stats_part = stats_part;
-      p.stats_swish = stats_swish;
-      p.c_block = y_block;
-      if (launch_stream(sp, p, stream, precision)) {
-        MLIIS_CHECK_LAUNCH("conv2d_fwd_stream");
-        if (stats_part != nullptr) *stats_nblk = sp.gx;
-        return MLIIS_OK;
-      }
-      p.stats_part = nullptr;
-      p.c_block = 0;
-    }
-    MLIIS_REQUIRE(y_block == 0, MLIIS_ERR_UNSUPPORTED, "conv2d_fwd: a group-blocked output needs the streamed 1x1 plan (mliis_conv2d_kernel_name)");
-    // long-K 1x1 convs on small maps (the MBConv project convs, SE gate on load): K split inside the workgroup, one launch
-    if (ksize == 1 && border_bias == nullptr && !ybf && M * ldx * 4 < (1LL << 31) && M * ldy * 4 < (1LL << 31) &&
-        (stats_part == nullptr || !accumulate) && (x_scale == nullptr || H * W >= 16) &&   // (the gate goes through LDS: two images per row group at most)
-        ksplit_plan(M, Cin, Cout, num_cus(), &sp)) {   // (its finishing threads write fp32)
-      MLIIS_REQUIRE(stats_part == nullptr || stats_nblk, MLIIS_ERR_ARG, "conv2d_fwd: fused statistics need a stats_nblk output");
-      p.stats_part = stats_part;
-      p.stats_swish = stats_swish;
-      if (launch_ksplit(sp, p, stream, precision)) {
-        MLIIS_CHECK_LAUNCH("conv2d_fwd_ksplit");
-        if (stats_part != nullptr) *stats_nblk = sp.gx;
-        return MLIIS_OK;
-      }
-      p.stats_part = nullptr;
-    }
+  MLIIS_REQUIRE(y_block == 0 || r.route == ROUTE_STREAM, MLIIS_ERR_UNSUPPORTED,
+                "conv2d_fwd: a group-blocked output needs the streamed 1x1 plan (mliis_conv2d_kernel_name)");
+  if (r.route != ROUTE_GEMM) {   // one launch; the statistics come from its finishing threads
+    MLIIS_REQUIRE(stats_part == nullptr || stats_nblk, MLIIS_ERR_ARG, "conv2d_fwd: fused statistics need a stats_nblk output");
+    p.stats_part = stats_part;
+    p.stats_swish = stats_swish;
+    p.c_block = y_block;
+    if ((rc = launch_1x1(r.route == ROUTE_STREAM ? "conv2d_fwd_stream" : "conv2d_fwd_ksplit", r, p, precision, false, stream))) return rc;
+    if (stats_part != nullptr) *stats_nblk = r.sp.gx;
+    return MLIIS_OK;
   }
   if (stats_part != nullptr) {   // fused BN statistics: GEMM epilogue (gz == 1) or the split-K fold (gz > 1)
     MLIIS_REQUIRE(!accumulate && stats_nblk, MLIIS_ERR_ARG, "conv2d_fwd: fused statistics need accumulate == 0 and a stats_nblk output");
@@ -633,37 +703,16 @@ int mliis_conv2d_fwd(const float* x, int ldx, const float* x_scale, const float*
       *stats_nblk = (int)((M + kRedRows - 1) / kRedRows);
     }
   }
-  if (g.gz > 1) {
-    size_t need = (size_t)g.gz * M * Cout;
-    MLIIS_REQUIRE(need <= ws_floats && aligned16(ws) && (ldy & 3) == 0 && aligned16(y), MLIIS_ERR_WORKSPACE,
-                  "conv2d_fwd: split-K workspace too small (%zu needed, %zu given) or unaligned output", need, ws_floats);
-    p.partial = ws;
-  }
-  float* sk_slab = nullptr;
-  if (g.sk_parts > 0 && x_scale == nullptr && ws != nullptr && aligned16(ws) && g.sk_slab_floats() <= ws_floats && (ldy & 3) == 0) sk_slab = ws;
-  launch_gemm(g, p, precision, stream, sk_slab);
-  MLIIS_CHECK_LAUNCH("conv2d_fwd");
-  if (g.gz > 1 && stats_part != nullptr) {
-    hipLaunchKernelGGL(splitk_reduce_stats_k, dim3((unsigned)((M + kRedRows - 1) / kRedRows), (Cout + 31) / 32), dim3(256), 0, stream, ws, g.gz,
-                       (int)M, Cout, y, ldy, bias, border_bias, H, W, stats_part, stats_swish);
-    MLIIS_CHECK_LAUNCH("conv2d_fwd_splitk_reduce_stats");
-  } else if (g.gz > 1) {
-    long long q = M * (Cout / 4);
-    int blocks = (int)((q + 255) / 256 > 2048 ? 2048 : (q + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce_k, dim3(blocks), dim3(256), 0, stream, ws, g.gz, M, Cout, y, ldy, bias, accumulate, border_bias, H, W);
-    MLIIS_CHECK_LAUNCH("conv2d_fwd_splitk_reduce");
-  }
-  return MLIIS_OK;
+  return launch_gemm_route("conv2d_fwd", g, p, ws, ws_floats, precision, g.gz > 1 ? stats_part : nullptr, stats_swish, stream);
 }
 
 // 1 when a 1x1 conv of this shape runs on the streaming plan, i.e. when mliis_conv2d_fwd_bnin accepts it (the MBConv expand convs:
 // Cin <= 112, N H W >= 1024); 0 otherwise.
 int mliis_conv2d_fwd_bnin_ok(int Nimg, int H, int W, int Cin, int Cout) {
-  StreamPlan sp;
-  const long long M = (long long)Nimg * H * W;
-  if (Nimg <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 3) || (Cout & 3) || M * Cin * 4 >= (1LL << 31) || M * Cout * 4 >= (1LL << 31))
-    return 0;
-  return stream_plan(M, Cin, Cout, num_cus(), &sp) ? 1 : 0;
+  if (Nimg <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 3) || (Cout & 3)) return 0;
+  ConvCall c = plain_call(Nimg, H, W, Cin, Cout, 1, false);
+  c.ain = true;
+  return route_conv(c).route == ROUTE_STREAM ? 1 : 0;
 }
 
 // y = conv1x1(a, w) with  a = ((z - mean) * rstd * gamma + beta) * img_scale[image] + res  formed while z is loaded: the plain batch
@@ -684,12 +733,9 @@ int mliis_conv2d_fwd_bnin(const float* z, int ldz, const float* bn_part, int bn_
   MLIIS_REQUIRE(z && bn_part && mean && rstd && gamma && beta && a_out && wt && y, MLIIS_ERR_ARG, "conv2d_fwd_bnin: null pointer");
   MLIIS_REQUIRE(bn_nblk > 0 && (moving_mean == nullptr) == (moving_var == nullptr), MLIIS_ERR_ARG,
                 "conv2d_fwd_bnin: needs stage-1 partials; the moving statistics come as a pair");
-  const int y_block = (y_dtype >> 8) & 0xff;
-  y_dtype &= 0xff;
-  MLIIS_REQUIRE(y_block == 0 || ((y_block == 2 || y_block == 4) && y_dtype == MLIIS_DT_F32 && Cout % y_block == 0), MLIIS_ERR_ARG,
-                "conv2d_fwd_bnin: a group-blocked output takes v = 2 | 4 dividing Cout and fp32 storage");
-  const bool ybf = y_dtype == MLIIS_DT_BF16;
-  MLIIS_REQUIRE(y_dtype == MLIIS_DT_F32 || ybf, MLIIS_ERR_ARG, "conv2d_fwd_bnin: bad storage type");
+  int y_block;
+  bool ybf;
+  if ((rc = out_dtype("conv2d_fwd_bnin", y_dtype, Cout, true, "Cout", &y_block, &ybf))) return rc;
   MLIIS_REQUIRE(!ybf || precision == MLIIS_PREC_BF16, MLIIS_ERR_UNSUPPORTED, "conv2d_fwd_bnin: a bf16 output needs MLIIS_PREC_BF16");
   MLIIS_REQUIRE((ldz & 3) == 0 && ldz >= Cin && (lda_out & 3) == 0 && lda_out >= Cin && (ldy & 3) == 0 && ldy >= Cout &&
                     (res == nullptr || ((ldr & 3) == 0 && ldr >= Cin)),
@@ -704,9 +750,14 @@ int mliis_conv2d_fwd_bnin(const float* z, int ldz, const float* bn_part, int bn_
   MLIIS_REQUIRE(precision != MLIIS_PREC_FP8 || (fp8_act_scale > 0.0f && fp8_w_amax != nullptr), MLIIS_ERR_ARG,
                 "conv2d_fwd_bnin: fp8 operands need a positive activation scale and the weight tensor's amax");
   MLIIS_REQUIRE(stats_part == nullptr || stats_nblk, MLIIS_ERR_ARG, "conv2d_fwd_bnin: fused statistics need a stats_nblk output");
-  StreamPlan sp;
-  MLIIS_REQUIRE(stream_plan(M, Cin, Cout, num_cus(), &sp), MLIIS_ERR_UNSUPPORTED,
-                "conv2d_fwd_bnin: not a streamed 1x1 shape (mliis_conv2d_fwd_bnin_ok)");
+  ConvCall c = plain_call(Nimg, H, W, Cin, Cout, 1, false);
+  c.lda = ldz;
+  c.ldc = ldy;
+  c.c_bf16 = ybf;
+  c.fwd_stats = stats_part != nullptr;
+  c.ain = true;
+  const RoutedConv r = route_conv(c);
+  MLIIS_REQUIRE(r.route == ROUTE_STREAM, MLIIS_ERR_UNSUPPORTED, "conv2d_fwd_bnin: not a streamed 1x1 shape (mliis_conv2d_fwd_bnin_ok)");
   ConvGemmParams p{z, ldz, Nimg, H, W, Cin, 1, 1, +1, wt, (long long)Cin * Cout, Cin, Cout, y, ldy,
                    nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, fp8_act_scale, fp8_w_amax};
   p.out_bf16 = ybf;
@@ -723,9 +774,8 @@ int mliis_conv2d_fwd_bnin(const float* z, int ldz, const float* bn_part, int bn_
   p.ain_out = a_out;
   p.ain_ldo = lda_out;
   if (stats_nblk) *stats_nblk = 0;
-  MLIIS_REQUIRE(launch_stream(sp, p, stream, precision, true), MLIIS_ERR_UNSUPPORTED, "conv2d_fwd_bnin: no instance <%d, %d>", sp.kc, sp.nt);
-  MLIIS_CHECK_LAUNCH("conv2d_fwd_bnin");
-  if (stats_part != nullptr) *stats_nblk = sp.gx;
+  if ((rc = launch_1x1("conv2d_fwd_bnin", r, p, precision, true, stream))) return rc;
+  if (stats_part != nullptr) *stats_nblk = r.sp.gx;
   return MLIIS_OK;
 }
 
@@ -794,13 +844,13 @@ static int conv2d_bwd_data_impl(const float* dy, int lddy, const float* w, float
   int rc = conv_check("conv2d_bwd_data", Nimg, H, W, Cin_out, Cout, ksize, dil);
   if (rc) return rc;
   if ((rc = prec_check("conv2d_bwd_data", precision))) return rc;
-  const int dx_block = (dx_dtype >> 8) & 0xff;   // MLIIS_DT_BLOCKED(v): dx in the group-blocked layout (as y in mliis_conv2d_fwd)
-  dx_dtype &= 0xff;
-  MLIIS_REQUIRE(dx_block == 0 || ((dx_block == 2 || dx_block == 4) && dx_dtype == MLIIS_DT_F32 && Cin_out % dx_block == 0 && ci_begin == 0 &&
-                                  Cin_out == Cin_total),
-                MLIIS_ERR_ARG, "conv2d_bwd_data: a group-blocked output takes v = 2 | 4 dividing the channel count, all channels and fp32 storage");
-  const bool dybf = dy_dtype == MLIIS_DT_BF16, dxbf = dx_dtype == MLIIS_DT_BF16;   // (as in mliis_conv2d_fwd)
-  MLIIS_REQUIRE((dy_dtype == MLIIS_DT_F32 || dybf) && (dx_dtype == MLIIS_DT_F32 || dxbf), MLIIS_ERR_ARG, "conv2d_bwd_data: bad storage type");
+  int dx_block;   // MLIIS_DT_BLOCKED(v): dx in the group-blocked layout (as y in mliis_conv2d_fwd)
+  bool dxbf;
+  if ((rc = out_dtype("conv2d_bwd_data", dx_dtype, Cin_out, ci_begin == 0 && Cin_out == Cin_total, "the channel count, all channels", &dx_block,
+                      &dxbf)))
+    return rc;
+  const bool dybf = dy_dtype == MLIIS_DT_BF16;   // (as in mliis_conv2d_fwd)
+  MLIIS_REQUIRE(dy_dtype == MLIIS_DT_F32 || dybf, MLIIS_ERR_ARG, "conv2d_bwd_data: bad storage type");
   if (dybf || dxbf) {
     MLIIS_REQUIRE(precision != MLIIS_PREC_FP32 && ksize == 1 && !(dxbf && accumulate), MLIIS_ERR_UNSUPPORTED,
                   "conv2d_bwd_data: bf16 tensors need bf16 operands, a 1x1 conv and (bf16 output) no accumulate");
@@ -815,82 +865,50 @@ static int conv2d_bwd_data_impl(const float* dy, int lddy, const float* w, float
   long long M = (long long)Nimg * H * W;
   MLIIS_REQUIRE(M * lddy * 4 < (1LL << 31) && (long long)ksize * ksize * Cin_total * Cout * 4 < (1LL << 31), MLIIS_ERR_UNSUPPORTED,
                 "conv2d_bwd_data: operand larger than 2 GiB (32-bit buffer offsets)");
-  GemmPlan g = plan_gemm(M, Cin_out, Cout, ksize * ksize, num_cus(), ws != nullptr);
+  ConvCall c = plain_call(Nimg, H, W, Cout, Cin_out, ksize, false);   // (backward-data: A = dy, reduction over Cout; no statistics of its own)
+  c.lda = lddy;
+  c.ldc = lddx;
+  c.a_bf16 = dybf;
+  c.c_bf16 = dxbf;
+  c.accumulate = accumulate != 0;
+  c.has_ws = ws != nullptr;
+  const RoutedConv r = route_conv(c);
+  const GemmPlan& g = r.g;
   if (precision == MLIIS_PREC_FP8) precision = MLIIS_PREC_BF16;   // fp8 mode: forward 1x1 convs in e4m3, the backward passes in bf16
   ConvGemmParams p{dy, lddy, Nimg, H, W, Cout, ksize * ksize, dil, -1, w + (long long)ci_begin * Cout, (long long)Cin_total * Cout,
                    Cout, Cin_out, dx, lddx, nullptr, accumulate, nullptr, g.chunks_per_split, nullptr, 0, nullptr, nullptr, 1.0f, nullptr};
   p.a_bf16 = dybf;
   p.out_bf16 = dxbf;
   p.side_bf16 = dxbf;
-  {  // short-K 1x1 convs (backward-data of the MBConv project convs): barrier-free streaming kernel
-    StreamPlan sp;
-    if (ksize == 1 && !accumulate && !dybf && M * lddx * 4 < (1LL << 31) && stream_plan(M, Cout, Cin_out, num_cus(), &sp)) {
-      const bool gate = bnb != nullptr && bnb->mean == nullptr;
-      const bool with_bn = bnb != nullptr && !gate && (size_t)sp.gx * 2 * Cin_out <= bnb->part_floats;
-      const bool with_gate = gate && (long long)H * W >= 16 && (size_t)sp.row_groups * 2 * Cin_out <= bnb->part_floats;
-      if (with_bn) {   // + stage 1 of the consumer batch norm's backward (per-wave sums, folded per block like the forward statistics)
-        p.stats_part = bnb->part;
-        p.bnb_x = bnb->x;
-        p.bnb_ldx = bnb->ldx;
-        p.bnb_mean = bnb->mean;
-        p.bnb_rstd = bnb->rstd;
-        p.bnb_scale = bnb->img_scale;
-      }
-      if (with_gate) {   // + per-row-group sums of dx * gate_x (the squeeze-excite gate's gradient)
-        p.gp_x = bnb->x;
-        p.gp_ldx = bnb->ldx;
-        p.gp_part = bnb->part;
-      }
-      p.c_block = dx_block;
-      if (launch_stream(sp, p, stream, precision)) {
-        MLIIS_CHECK_LAUNCH("conv2d_bwd_data_stream");
-        if (with_bn) *bnb->nblk = sp.gx;
-        if (with_gate) *bnb->nblk = sp.row_groups;
-        return MLIIS_OK;
-      }
-      p.stats_part = nullptr;
-      p.bnb_x = nullptr;
-      p.gp_part = nullptr;
-      p.c_block = 0;
+  MLIIS_REQUIRE(dx_block == 0 || r.route == ROUTE_STREAM, MLIIS_ERR_UNSUPPORTED, "conv2d_bwd_data: a group-blocked output needs the streamed 1x1 plan");
+  if (r.route != ROUTE_GEMM) {
+    const StreamPlan& sp = r.sp;
+    const bool gate = bnb != nullptr && bnb->mean == nullptr;
+    // + stage 1 of the consumer batch norm's backward (stream: per-wave sums, folded per block like the forward statistics; ksplit:
+    // from the finishing threads)
+    const bool with_bn = bnb != nullptr && !gate && (size_t)sp.gx * 2 * Cin_out <= bnb->part_floats;
+    // + per-row-group sums of dx * gate_x (the squeeze-excite gate's gradient): the streaming kernel only
+    const bool with_gate = gate && r.route == ROUTE_STREAM && (long long)H * W >= 16 && (size_t)sp.row_groups * 2 * Cin_out <= bnb->part_floats;
+    if (with_bn) {
+      p.stats_part = bnb->part;
+      p.bnb_x = bnb->x;
+      p.bnb_ldx = bnb->ldx;
+      p.bnb_mean = bnb->mean;
+      p.bnb_rstd = bnb->rstd;
+      p.bnb_scale = bnb->img_scale;
     }
-    MLIIS_REQUIRE(dx_block == 0, MLIIS_ERR_UNSUPPORTED, "conv2d_bwd_data: a group-blocked output needs the streamed 1x1 plan");
-    // long-K 1x1 convs on small maps (backward-data of the MBConv expand convs): K split inside the workgroup, one launch
-    if (ksize == 1 && !dxbf && M * lddx * 4 < (1LL << 31) && M * lddy * 4 < (1LL << 31) && ksplit_plan(M, Cout, Cin_out, num_cus(), &sp)) {
-      const bool with_bn = bnb != nullptr && bnb->mean != nullptr && (size_t)sp.gx * 2 * Cin_out <= bnb->part_floats;
-      if (with_bn) {   // + stage 1 of the consumer batch norm's backward from the finishing threads
-        p.stats_part = bnb->part;
-        p.bnb_x = bnb->x;
-        p.bnb_ldx = bnb->ldx;
-        p.bnb_mean = bnb->mean;
-        p.bnb_rstd = bnb->rstd;
-        p.bnb_scale = bnb->img_scale;
-      }
-      if (launch_ksplit(sp, p, stream, precision)) {
-        MLIIS_CHECK_LAUNCH("conv2d_bwd_data_ksplit");
-        if (with_bn) *bnb->nblk = sp.gx;
-        return MLIIS_OK;
-      }
-      p.stats_part = nullptr;
-      p.bnb_x = nullptr;
+    if (with_gate) {
+      p.gp_x = bnb->x;
+      p.gp_ldx = bnb->ldx;
+      p.gp_part = bnb->part;
     }
+    p.c_block = dx_block;
+    if ((rc = launch_1x1(r.route == ROUTE_STREAM ? "conv2d_bwd_data_stream" : "conv2d_bwd_data_ksplit", r, p, precision, false, stream))) return rc;
+    if (with_bn) *bnb->nblk = sp.gx;
+    if (with_gate) *bnb->nblk = sp.row_groups;
+    return MLIIS_OK;
   }
-  if (g.gz > 1) {
-    size_t need = (size_t)g.gz * M * Cin_out;
-    MLIIS_REQUIRE(need <= ws_floats && aligned16(ws) && (lddx & 3) == 0 && aligned16(dx), MLIIS_ERR_WORKSPACE,
-                  "conv2d_bwd_data: split-K workspace too small (%zu needed, %zu given) or unaligned output", need, ws_floats);
-    p.partial = ws;
-  }
-  float* sk_slab = nullptr;
-  if (g.sk_parts > 0 && ws != nullptr && aligned16(ws) && g.sk_slab_floats() <= ws_floats && (lddx & 3) == 0) sk_slab = ws;
-  launch_gemm(g, p, precision, stream, sk_slab);
-  MLIIS_CHECK_LAUNCH("conv2d_bwd_data");
-  if (g.gz > 1) {
-    long long q = M * (Cin_out / 4);
-    int blocks = (int)((q + 255) / 256 > 2048 ? 2048 : (q + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce_k, dim3(blocks), dim3(256), 0, stream, ws, g.gz, M, Cin_out, dx, lddx, nullptr, accumulate, nullptr, H, W);
-    MLIIS_CHECK_LAUNCH("conv2d_bwd_data_splitk_reduce");
-  }
-  return MLIIS_OK;
+  return launch_gemm_route("conv2d_bwd_data", g, p, ws, ws_floats, precision, nullptr, 0, stream);
 }
 
 // desc: device int32 [ndesc][4] = {offset (floats), taps, Cin, Cout}; src/dst: arenas with identical layout.

@@ -1603,24 +1603,57 @@ static void launch_gemm_t(const GemmPlan& g, const ConvGemmParams& p, hipStream_
 #undef NK
 }
 
-// conv1x1_ksplit_k instances: KC 16-wide K groups per wave (8 waves: K <= 128 KC), NT column tiles, KC * NT <= 8, NT <= 7; and the
+// The instances of the two 1x1 kernel families, one list each: the launch switches, the routing (route_conv: a planned <KC, NT> without
+// an instance takes the GEMM) and mliis_conv1x1_occupancy are all derived from these.
+// conv1x1_stream_k: X(KC, NT, AIN): KC 16-wide K groups (K <= 112), NT column tiles per wave, KC * NT <= 8; AIN = 0: no
+// conv1x1_stream_k<..., AIN = true> form (the planner never gives more than four column tiles)
+#define MLIIS_STREAM_INSTANCES(X)                                                                                            \
+  X(1, 1, 1) X(1, 2, 1) X(1, 3, 1) X(1, 4, 1) X(1, 5, 0) X(1, 6, 0) X(1, 7, 0) X(1, 8, 0) X(2, 1, 1) X(2, 2, 1) X(2, 3, 1) \
+  X(2, 4, 1) X(3, 1, 1) X(3, 2, 1) X(4, 1, 1) X(4, 2, 1) X(5, 1, 1) X(6, 1, 1) X(7, 1, 1)
+// conv1x1_ksplit_k: X(KC, NT): KC 16-wide K groups per wave (8 waves: K <= 128 KC), NT column tiles, KC * NT <= 8, NT <= 7; and the
 // three instances with KC * NT = 12 that the planner takes on the small maps (one workgroup per CU there: 256 registers)
+#define MLIIS_KSPLIT_INSTANCES(X)                                                                                  \
+  X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 5) X(1, 6) X(1, 7) X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(3, 1) X(3, 2) X(4, 1) \
+  X(4, 2) X(4, 3) X(5, 1) X(5, 2) X(6, 1) X(6, 2) X(7, 1)
+
+static inline bool stream_instance(int kc, int nt, bool ain) {
+#define X(KC_, NT_, AIN_) if (kc == KC_ && nt == NT_) return !ain || AIN_;
+  MLIIS_STREAM_INSTANCES(X)
+#undef X
+  return false;
+}
+static inline bool ksplit_instance(int kc, int nt) {
+#define X(KC_, NT_) if (kc == KC_ && nt == NT_) return true;
+  MLIIS_KSPLIT_INSTANCES(X)
+#undef X
+  return false;
+}
+
+// false: no such instance (nothing launched)
+template <int PREC, bool AIN>
+static bool launch_stream_t(int kc, int nt, dim3 grid, const ConvGemmParams& p, int row_groups, hipStream_t stream) {
+  dim3 block(64 * kStreamWaves);
+#define X(KC_, NT_, AIN_)                                                                                               \
+  if constexpr (!AIN || AIN_)                                                                                           \
+    if (kc == KC_ && nt == NT_) {                                                                                       \
+      hipLaunchKernelGGL((conv1x1_stream_k<KC_, NT_, PREC, AIN>), grid, block, 0, stream, p, row_groups);              \
+      return true;                                                                                                      \
+    }
+  MLIIS_STREAM_INSTANCES(X)
+#undef X
+  return false;
+}
 template <int PREC>
 static bool launch_ksplit_t(int kc, int nt, dim3 grid, const ConvGemmParams& p, int row_groups, hipStream_t stream) {
   dim3 block(512);
-#define S(KC_, NT_) hipLaunchKernelGGL((conv1x1_ksplit_k<KC_, NT_, 8, PREC>), grid, block, 0, stream, p, row_groups); break;
-  switch (kc) {
-    case 1: switch (nt) { case 1: S(1, 1) case 2: S(1, 2) case 3: S(1, 3) case 4: S(1, 4) case 5: S(1, 5) case 6: S(1, 6) case 7: S(1, 7) default: return false; } break;
-    case 2: switch (nt) { case 1: S(2, 1) case 2: S(2, 2) case 3: S(2, 3) case 4: S(2, 4) default: return false; } break;
-    case 3: switch (nt) { case 1: S(3, 1) case 2: S(3, 2) default: return false; } break;
-    case 4: switch (nt) { case 1: S(4, 1) case 2: S(4, 2) case 3: S(4, 3) default: return false; } break;
-    case 5: switch (nt) { case 1: S(5, 1) case 2: S(5, 2) default: return false; } break;
-    case 6: switch (nt) { case 1: S(6, 1) case 2: S(6, 2) default: return false; } break;
-    case 7: switch (nt) { case 1: S(7, 1) default: return false; } break;
-    default: return false;
+#define X(KC_, NT_)                                                                                        \
+  if (kc == KC_ && nt == NT_) {                                                                            \
+    hipLaunchKernelGGL((conv1x1_ksplit_k<KC_, NT_, 8, PREC>), grid, block, 0, stream, p, row_groups);     \
+    return true;                                                                                           \
   }
-#undef S
-  return true;
+  MLIIS_KSPLIT_INSTANCES(X)
+#undef X
+  return false;
 }
 
 struct FilterPlan {

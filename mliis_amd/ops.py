@@ -150,6 +150,19 @@ def conv2d_plan(N, H, W, cred, nout, k):
     return tm.value, nt.value, sp.value
 
 
+def _conv_meta(N, H, W, cin, cout, k, dil, bwd=False, has_scale=False, precision="fp32", splits=None, x3=False):
+    """The PROFILE record of a dense-conv call ({} when not profiling).  bwd: backward-data (the reduction runs over cout); splits: given
+    when the call does not follow conv2d_plan; x3: a split-product call (conv_x3.hip)."""
+    if PROFILE is None:
+        return {}
+    cred, nout = (cout, cin) if bwd else (cin, cout)
+    meta = dict(flops=2.0 * N * H * W * k * k * cin * cout, shape=(N, H, W, cin, cout, k, dil))
+    if x3:
+        return dict(kernel=conv2d_x3_kernel_name(N, H, W, cred, nout, k), **meta)
+    return dict(kernel=conv2d_kernel_name(N, H, W, cred, nout, k, has_scale, precision),
+                splits=conv2d_plan(N, H, W, cred, nout, k)[2] if splits is None else splits, **meta)
+
+
 class Workspace:
     """Grow-only scratch buffer (floats) shared by all calls on a stream.  `on_grow` (optional) is called BEFORE the buffer is
     replaced: an owner whose captured HIP graphs have the old address baked in must drop them there (Learner does)."""
@@ -482,11 +495,7 @@ def conv2d_fwd(x, w, bias=None, dil=1, out=None, accumulate=False, ws: Optional[
     _, co, ldy = rows_ld(out)
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_conv2d_workspace_floats", N, H, W, Cin, Cout, k))
-    meta = {}
-    if PROFILE is not None:
-        tm, nt, sp = conv2d_plan(N, H, W, Cin, Cout, k)
-        meta = dict(kernel=conv2d_kernel_name(N, H, W, Cin, Cout, k, x_scale is not None, precision), splits=sp,
-                    flops=2.0 * N * H * W * k * k * Cin * Cout, shape=(N, H, W, Cin, Cout, k, dil))
+    meta = _conv_meta(N, H, W, Cin, Cout, k, dil, has_scale=x_scale is not None, precision=precision)
     nblk = C.c_int(0)
     prec = _prec(precision)
     if prec == 2 and k == 1 and fp8_w_amax is None:   # stand-alone call: take the tensor's amax here (the learner gets it from the
@@ -533,10 +542,7 @@ def conv2d_fwd_bnin(z, part, nblk, mean, rstd, gamma, beta, a_out, w, out, movin
         fp8_w_amax = w.abs().max().reshape(1)
     if stats_part is not None and stats_part.numel() < (-(-N * H * W // 16)) * 2 * Cout:
         raise MliisError("conv2d_fwd_bnin: stats_part too small")
-    meta = {}
-    if PROFILE is not None:
-        meta = dict(kernel=conv2d_kernel_name(N, H, W, Cin, Cout, 1, False, precision), splits=1, flops=2.0 * N * H * W * Cin * Cout,
-                    shape=(N, H, W, Cin, Cout, 1, 1))
+    meta = _conv_meta(N, H, W, Cin, Cout, 1, 1, precision=precision, splits=1)
     nb = C.c_int(0)
     _timed("conv2d_fwd", meta, lambda: lib.call("mliis_conv2d_fwd_bnin", _ptr(_chk(z)), ldz, _ptr(part), int(nblk), eps, momentum, _ptr(mean), _ptr(rstd),
                                                 _ptr(mm), _ptr(mv), _ptr(gamma), _ptr(beta), _ptr(img_scale), _ptr(res), ldr, _ptr(a_out), ldo,
@@ -618,9 +624,7 @@ def conv2d_fwd_x3(x, image, k, cout, bias=None, dil=1, out=None, accumulate=Fals
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_conv2d_x3_workspace_floats", N, H, W, Cin, cout, k))
     nblk = C.c_int(0)
-    meta = {}
-    if PROFILE is not None:
-        meta = dict(kernel=conv2d_x3_kernel_name(N, H, W, Cin, cout, k), flops=2.0 * N * H * W * k * k * Cin * cout, shape=(N, H, W, Cin, cout, k, dil))
+    meta = _conv_meta(N, H, W, Cin, cout, k, dil, x3=True)
     _timed("conv2d_fwd_x3", meta, lambda: lib.call("mliis_conv2d_fwd_x3", _aptr(x), ldx, _ptr(image), image.numel() * image.element_size(), _ptr(bias), _ptr(border_bias), _aptr(out), ldy,
                                                    N, H, W, Cin, cout, k, dil, int(accumulate), _ptr(stats_part), int(stats_swish), C.byref(nblk),
                                                    _ptr(buf), buf.numel(), _stream()))
@@ -639,9 +643,7 @@ def conv2d_bwd_data_x3(dy, image, k, cin_out, dil=1, out=None, accumulate=False,
     _, ci, lddx = rows_ld(out)
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_conv2d_x3_workspace_floats", N, H, W, Cout, cin_out, k))
-    meta = {}
-    if PROFILE is not None:
-        meta = dict(kernel=conv2d_x3_kernel_name(N, H, W, Cout, cin_out, k), flops=2.0 * N * H * W * k * k * cin_out * Cout, shape=(N, H, W, Cout, cin_out, k, dil))
+    meta = _conv_meta(N, H, W, Cout, cin_out, k, dil, x3=True)   # (recorded as the GEMM it is: reduction width first)
     _timed("conv2d_bwd_data_x3", meta, lambda: lib.call("mliis_conv2d_bwd_data_x3", _aptr(dy), lddy, _ptr(image), image.numel() * image.element_size(), _aptr(out), lddx, N, H, W, cin_out,
                                                         Cout, k, dil, int(accumulate), _ptr(buf), buf.numel(), _stream()))
     return out
@@ -672,11 +674,7 @@ def conv2d_bwd_data(dy, w, dil=1, ci_begin=0, ci_count=None, out=None, accumulat
     ws = ws or default_ws()
     buf = ws.get(lib.size("mliis_conv2d_workspace_floats", N, H, W, Cout, ci_count, k))
     prec = _prec(precision)
-    meta = {}
-    if PROFILE is not None:
-        tm, nt, sp = conv2d_plan(N, H, W, Cout, ci_count, k)
-        meta = dict(kernel=conv2d_kernel_name(N, H, W, Cout, ci_count, k, False, precision), splits=sp, flops=2.0 * N * H * W * k * k * ci_count * Cout,
-                    shape=(N, H, W, ci_count, Cout, k, dil))
+    meta = _conv_meta(N, H, W, ci_count, Cout, k, dil, bwd=True, precision=precision)
     if gate is not None:   # out is the gradient w.r.t. gate_x * gate: the launch may leave the gate-gradient partials in `part`
         groups = C.c_int(0)
         _timed("conv2d_bwd_data", meta, lambda: lib.call("mliis_conv2d_bwd_data_gate", _aptr(dy), lddy, _ptr(w), _aptr(out), lddx, N, H, W, Cin,

@@ -1161,6 +1161,37 @@ def test_streamed_1x1_convs_write_the_group_blocked_layout(N, H, Cin, Cout, V):
         ops.conv2d_fwd(f32(rnd(N, H, H, 480, seed=6), d), f32(rnd(1, 1, 480, 80, seed=7), d), None, 1, out_block=4)
 
 
+def test_a_1x1_conv_whose_output_view_passes_2_gib_takes_the_gemm():
+    """The 1x1 kernels address their operands with 32-bit byte offsets, so the routing sends a call with M * ldy * 4 >= 2^31 to the GEMM
+    (64-bit row offsets) although the shape is a streamed one: 1024 rows of 32 channels written as a channel-slice view whose row stride
+    puts the last row just past 2 GiB.  Same values as the dense (streamed) call, and the statistics come per GEMM row block.
+    (Small-integer operands: every product and sum is exact in fp32, so the two kernels' different summation orders cannot show and the
+    comparison is bit for bit.)"""
+    from mliis_amd import ops
+    d = dev()
+    N, H, Cin, Cout = 1, 32, 16, 32
+    M, ld = N * H * H, (1 << 19) + 4
+    assert (M - 1) * ld * 4 < 2 ** 31 <= M * ld * 4
+    assert ops.conv1x1_stream_eligible(N, H, H, Cin, Cout)
+    tm, _, splits = ops.conv2d_plan(N, H, H, Cin, Cout, 1)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randint(-4, 5, (N, H, H, Cin), generator=g).float().to(d)
+    w = torch.randint(-4, 5, (1, 1, Cin, Cout), generator=g).float().to(d)
+    pa, pb = torch.zeros(1 << 13, device=d), torch.zeros(1 << 13, device=d)
+    y, na = ops.conv2d_fwd(x, w, None, 1, stats_part=pa)
+    try:
+        big = torch.empty(M * ld, device=d)
+    except RuntimeError as e:   # (torch.cuda.OutOfMemoryError is one)
+        pytest.skip("no room for the 2 GiB allocation the padded view is taken from: {}".format(e))
+    out = big.view(N, H, H, ld)[..., 8:8 + Cout]
+    out.fill_(9.0)
+    yb, nb = ops.conv2d_fwd(x, w, None, 1, stats_part=pb, out=out)
+    assert torch.equal(yb, y)
+    assert splits == 1 and nb == -(-M // (64 * tm)) and nb != na, (na, nb, tm, splits)
+    sums = lambda p, n: p[:n * 2 * Cout].view(n, 2, Cout).double().sum(0)   # noqa: E731
+    assert torch.equal(sums(pa, na), sums(pb, nb))   # (exact as well: block sums below 2^24)
+
+
 # ------------------------------------------------------------------------------------------------ data-parallel + stream-K remainder
 @pytest.mark.parametrize("k,dil,H,Cin,Cout,N", [(3, 1, 56, 72, 112, 8), (3, 2, 56, 64, 136, 8), (3, 1, 56, 56, 224, 8), (1, 1, 64, 512, 112, 9)])   # (the 1x1 case: 36864 rows, beyond the in-workgroup K split of the small maps)
 def test_conv2d_stream_k_remainder(k, dil, H, Cin, Cout, N):
