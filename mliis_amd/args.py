@@ -111,7 +111,9 @@ _EXT = [
                                help="worker processes for the pixel half of --augment (-1: host cores - 1, 0: inline like the reference)")),
     ("--concurrent-tasks", dict(type=int, default=1,
                                 help="adapt this many tasks of a meta-batch at once on separate learners / streams (same meta-update; "
-                                     "4 is the optimum on MI355X, needs meta_batch_size / ranks >= 2 to matter)")),
+                                     "4 is the optimum on MI355X, needs meta_batch_size / ranks >= 2 to matter).  Also with --augment "
+                                     "(pixels on the device: every learner augments its own batches); --augment-on-host adapts one task "
+                                     "at a time")),
     ("--matmul-precision", dict(choices=["fp32", "fp32-native", "bf16", "fp8", "bf16-storage"], default="fp32",
                                 help="operand precision of the matrix cores in the dense convs (bf16: fp32 tensors rounded on the fly, fp32 accumulation); "
                                      "bf16-storage: bf16 operands and the expanded MBConv tensors (z0, z1, a1, their gradients) as bf16 in HBM during "

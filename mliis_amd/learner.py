@@ -138,12 +138,7 @@ class Learner(_Passes):
         self.shots_x = torch.zeros(max_shots + self.aug_capacity, H, H, 3, dtype=torch.float32, device=self.device)
         self.shots_y = torch.zeros(max_shots + self.aug_capacity, H, H, 2, dtype=torch.float32, device=self.device)
         if self.aug_capacity:
-            self._aug_tmp_x = torch.zeros(self.aug_capacity, H, H, 3, dtype=torch.float32, device=self.device)
-            self._aug_tmp_y = torch.zeros(self.aug_capacity, H, H, 2, dtype=torch.float32, device=self.device)
-            self._aug_ops_dev = torch.zeros(8 * self.aug_capacity * 48, dtype=torch.uint8, device=self.device)
-            self._aug_ops_pin = torch.zeros((4, 8 * self.aug_capacity * 48), dtype=torch.uint8).pin_memory()
-            self._aug_ev = [None] * 4
-            self._aug_n = 0
+            self._alloc_augment_buffers()
         self.n_shots = 0
         self._aug_valid = 0   # samples of the last augment_batch() behind the resident shots (load_task() invalidates them)
         # device RNG of the stochastic ops (drop-connect, dropout): Philox state advanced by the mask kernel itself (csrc/rng.hip)
@@ -393,6 +388,40 @@ class Learner(_Passes):
             self.shots_y[:S].copy_(labels.to(torch.float32), non_blocking=True)
         self.n_shots = S
         self._aug_valid = 0
+
+    def _alloc_augment_buffers(self):
+        """What augment_batch() needs besides the batch slots behind the shots: the ping-pong buffers of a multi-stage recipe, the device
+        copy of a batch's encoded stages and the ring of pinned slots (with their events) it is uploaded through."""
+        H = self.arch.image_size
+        self._aug_tmp_x = torch.zeros(self.aug_capacity, H, H, 3, dtype=torch.float32, device=self.device)
+        self._aug_tmp_y = torch.zeros(self.aug_capacity, H, H, 2, dtype=torch.float32, device=self.device)
+        self._aug_ops_dev = torch.zeros(8 * self.aug_capacity * 48, dtype=torch.uint8, device=self.device)
+        self._aug_ops_pin = torch.zeros((4, 8 * self.aug_capacity * 48), dtype=torch.uint8).pin_memory()
+        self._aug_ev = [None] * 4
+        self._aug_n = 0
+
+    def reserve_augment_capacity(self, n: int):
+        """Give a learner that was built with fewer (or no) augmentation slots `n` of them (augment_batch_capacity=n after the fact): the
+        resident shots move into a larger allocation with the batch slots behind them, contents kept.  Captured graphs hold the old
+        address and a plan may have been sized against it, so this is only allowed while the learner has neither."""
+        n = int(n)
+        if self.plans:
+            raise ValueError("reserve_augment_capacity: the learner has already stepped (plans / captured graphs hold the shot buffers)")
+        if n <= self.aug_capacity:
+            return
+        H = self.arch.image_size
+        self.stream.synchronize()
+        self._in()
+        with torch.cuda.stream(self.stream):
+            for name, ch in (("shots_x", 3), ("shots_y", 2)):
+                old = getattr(self, name)
+                new = torch.zeros(self.max_shots + n, H, H, ch, dtype=torch.float32, device=self.device)
+                new[:old.shape[0]].copy_(old)
+                setattr(self, name, new)
+        self.aug_capacity = n
+        self._alloc_augment_buffers()
+        self._aug_valid = 0
+        torch.cuda.synchronize(self.device)   # (the old buffers are released and the new ones zeroed before anything else runs)
 
     def augment_batch(self, src_idx: Sequence[int], recipes) -> List[int]:
         """On-device augmentation of one mini-batch (csrc/augment.hip): sample b = shot src_idx[b] of the resident task through the

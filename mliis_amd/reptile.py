@@ -133,7 +133,8 @@ class Gecko:
         # rank are then adapted len(lanes)+1 at a time, their inner steps issued round-robin so the launches of one task fill the
         # compute units the other leaves idle (one 8-image step alone does not fill 256 CUs: profiles/r01_notes.md).  Same update as
         # task-by-task -- the tasks are independent and the deltas are accumulated in task order -- except that every lane draws its
-        # drop-connect masks from its own generator.
+        # drop-connect masks from its own generator.  With augment="device" as well: a task's whole schedule is drawn on the host before
+        # its first step and the pixels are made on the learner that steps on them (_lanes_in_use).
         self.lanes = list(lanes)
         # Adam (the reference's default inner optimizer): every lane keeps its own second-moment slots and step count, exactly as every
         # RANK does under multi-GPU sharding -- the reference's single sequential history over all tasks is not
@@ -171,6 +172,8 @@ class Gecko:
             self.augmenter = Augmenter(fields=not self.device_aug)
             if self.device_aug and not getattr(learner, "aug_capacity", 0):
                 raise ValueError("augment='device' needs a learner built with augment_batch_capacity >= the inner batch size")
+        # device augmentation on the lanes: every lane needs the main learner's batch slots; one built without them is extended here
+        self._lanes_augment = bool(self.device_aug and self.lanes and self._extend_lanes())
         print("Augmentation rate {}".format(self.aug_rate))
         if self.rng_mode == "reference" and self.dist.world > 1:
             raise ValueError("rng_mode='reference' consumes the global generator sequentially and is only valid on one rank")
@@ -180,6 +183,28 @@ class Gecko:
         print("{} meta-learning session instantiated ({} rank(s), rng_mode={}).".format(self.meta_fn, self.dist.world, self.rng_mode))
 
     # ------------------------------------------------------------------------------------------------ helpers
+    def _extend_lanes(self) -> bool:
+        """Learner.reserve_augment_capacity on every lane with fewer augmentation slots than the main learner.  False -- after one printed
+        line -- when a lane cannot be extended (it has stepped already, or has no such method): the task-by-task loop is used then."""
+        want = int(self.learner.aug_capacity)
+        for k, ln in enumerate(self.lanes):
+            if int(getattr(ln, "aug_capacity", 0)) >= want:
+                continue
+            reserve = getattr(ln, "reserve_augment_capacity", None)
+            try:
+                if reserve is None:
+                    raise ValueError("it has no reserve_augment_capacity()")
+                reserve(want)
+            except ValueError as e:
+                print("Lane {} cannot take {} augmentation slots ({}): tasks are adapted one at a time.".format(k + 1, want, e))
+                return False
+        return True
+
+    def _lanes_in_use(self) -> bool:
+        """Whether the tasks go over the lanes: without augmentation, or with the pixels made on the device and every lane able to make
+        them.  The host-pixel augmenter uploads its batches step by step into the main learner: task by task."""
+        return bool(self.lanes) and (self.augmenter is None or self._lanes_augment)
+
     def _rng(self, task_idx: int):
         return None if self.rng_mode == "reference" else _task_rng(self.seed, self.meta_iter, task_idx)
 
@@ -197,9 +222,9 @@ class Gecko:
 
     _train_aug_rate_from_self = False   # Reptile's train_step does not forward aug_rate to _mini_batches (reptile.py:108); FOMAML does
 
-    def _augmented_task_schedule(self, inner_batch_size, inner_iters, replacement, rng, task_idx):
+    def _augmented_task_schedule(self, inner_batch_size, inner_iters, replacement, rng, task_idx, task=None):
         """Draws one task's augmented inner-loop schedule (all generator consumption happens here, in the reference's order) and hands
-        the pixel work to the pool, if there is one."""
+        the pixel work to the pool, if there is one.  `task`: its (images, labels); default the task _sample() made resident last."""
         if rng is not None:   # per-task mode: private, reproducible streams for the augmenter as well
             import numpy as np
             from .augment import PRISTINE_ORDER
@@ -207,7 +232,7 @@ class Gecko:
             self.augmenter.npr = np.random.RandomState(_task_rng(self.seed, self.meta_iter, task_idx).getrandbits(32))
             self.augmenter.order = list(PRISTINE_ORDER)   # the reference's persistent shuffled order would make a task's draws depend on
             #                                              which tasks this rank saw before (i.e. on the rank count): start every task fresh
-        x, y = self._host_task
+        x, y = self._host_task if task is None else task
         wr = getattr(self, "sample_train_val_with_replacement", False)
         sched = metaseg.AugmentedSchedule(x, y, inner_batch_size, inner_iters, replacement, self.augmenter,
                                           self.aug_rate if self._train_aug_rate_from_self else None, rng,
@@ -243,7 +268,7 @@ class Gecko:
                     rng = self._rng(t)
                     self._sample(dataset, num_shots, rng)
                     ahead[t] = self._augmented_task_schedule(inner_batch_size, inner_iters, replacement, rng, t)
-            if self.lanes and self.augmenter is None:
+            if self._lanes_in_use():
                 self._adapt_concurrently(mine, dataset, num_shots, inner_batch_size, inner_iters, replacement, meta_batch_size, lr, fomaml,
                                          old, delta, bn_acc)
                 mine = []
@@ -300,7 +325,11 @@ class Gecko:
                         if torch.is_tensor(a) and a.is_cuda:
                             a.record_stream(lane.stream)
                 lane.load_task(images, labels)
-                batches = self._task_batches(int(images.shape[0]), inner_batch_size, inner_iters, replacement, rng)
+                if self.device_aug:   # the whole schedule with its per-sample recipes, drawn now: (recipes, shot indices) per step
+                    batches = self._augmented_task_schedule(inner_batch_size, inner_iters, replacement, rng, t,
+                                                            task=(images, labels)).device_batches()
+                else:
+                    batches = self._task_batches(int(images.shape[0]), inner_batch_size, inner_iters, replacement, rng)
                 if lane is not L:
                     lane.import_trainable(old)
                 lane.import_bn(self._bn_zero)
@@ -311,7 +340,10 @@ class Gecko:
                     if j < len(batches):
                         if fomaml and j == inner_iters - 1:
                             g[3] = lane.export_trainable()
-                        self._step(batches[j], j, lr, lane)
+                        idx = batches[j]
+                        if self.device_aug:   # on the lane's own stream: step j + 1's pixels replace the slots step j's graph read
+                            idx = self._device_batch(lane, idx[1], idx[0])
+                        self._step(idx, j, lr, lane)
             for lane, t, _, last_backup in group:
                 L.axpby(1.0, lane.export_trainable(), 1.0, delta)
                 L.axpby(-1.0, last_backup if fomaml else old, 1.0, delta)
@@ -383,9 +415,9 @@ class Gecko:
             random.shuffle(dataset)
             sampled = dataset[:num_tasks_to_sample]
         ious, task_iou_map = [], {}
-        if self.lanes and self.augmenter is None and not save_fine_tuned_checkpoints:
+        if self._lanes_in_use() and not save_fine_tuned_checkpoints:
             for name, iou in self._evaluate_concurrently(sampled, num_shots, test_shots, inner_batch_size, inner_iters, replacement, lr,
-                                                         drop_rate):
+                                                         drop_rate, self.aug_rate if aug_rate is None else aug_rate):
                 ious.append(iou)
                 task_iou_map[name] = iou
             sampled = []
@@ -404,10 +436,12 @@ class Gecko:
         print("Mean IoU from train on {} images and evaluate on {} test images: {}".format(num_shots, test_shots, mean_iou))
         return mean_iou, task_iou_map
 
-    def _evaluate_concurrently(self, sampled, num_shots, test_shots, inner_batch_size, inner_iters, replacement, lr, drop_rate):
+    def _evaluate_concurrently(self, sampled, num_shots, test_shots, inner_batch_size, inner_iters, replacement, lr, drop_rate,
+                               aug_rate=None):
         """evaluate's task loop over the lanes: every task of a group is fine-tuned from the same restored state on a learner of
-        its own, the steps issued round-robin; host draws (example sampling, mini-batch schedule) stay in task order and the
-        predictions / IoUs are taken task by task afterwards, so the result equals the sequential loop's."""
+        its own, the steps issued round-robin; host draws (example sampling, mini-batch schedule and, with device augmentation, the
+        per-sample recipes) stay in task order and the predictions / IoUs are taken task by task afterwards, so the result equals the
+        sequential loop's."""
         import numpy as np
         from .metrics import iou as _iou
         L = self.learner
@@ -419,7 +453,13 @@ class Gecko:
             for lane, task in zip(lanes, sampled[g0:g0 + len(lanes)]):
                 (images, labels), name = metaseg.sample_task([task], num_shots + test_shots, None, return_task_name=True)
                 train_idx, test_idx = metaseg.split_indices(int(images.shape[0]), test_shots)
-                schedule = [list(b) for b in metaseg.mini_batch_indices(len(train_idx), inner_batch_size, inner_iters, replacement)]
+                if self.device_aug:   # as _evaluate draws them: (recipe, position in train_idx) per sample, all before the first step
+                    shape, keep_p = tuple(images.shape[1:]), None if aug_rate is None else 1.0 - aug_rate
+                    visit = lambda i: (self.augmenter.plan(shape, keep_p), i)   # noqa: E731
+                else:
+                    visit = None
+                schedule = [list(b) for b in metaseg.mini_batch_indices(len(train_idx), inner_batch_size, inner_iters, replacement,
+                                                                        visit=visit)]
                 if lane is not L:
                     lane.import_all(state)
                 lane.load_task(images, labels)
@@ -427,7 +467,11 @@ class Gecko:
             for j in range(max(len(g[6]) for g in group)):
                 for lane, _, _, _, train_idx, _, schedule in group:
                     if j < len(schedule):
-                        self._fine_tune_step([train_idx[i] for i in schedule[j]], j, lr, self.lr_scheduler, drop_rate, lane)
+                        if self.device_aug:
+                            idx = self._device_batch(lane, [train_idx[i] for (_, i) in schedule[j]], [r for (r, _) in schedule[j]])
+                        else:
+                            idx = [train_idx[i] for i in schedule[j]]
+                        self._fine_tune_step(idx, j, lr, self.lr_scheduler, drop_rate, lane)
             for lane, name, _, labels, train_idx, test_idx, _ in group:
                 if self.device_metrics:
                     class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane)))

@@ -177,8 +177,13 @@ def main(argv=None, learner_factory=None, device=None):
     _validate_datasets(args, train_set, val_set, test_set)
 
     lanes = []
-    if args.concurrent_tasks > 1 and not args.augment:   # the augmented path uploads host batches step by step: one lane
-        lanes = [Learner(device=device, **dict(model_kwargs(args), seed=args.seed + 1000 * k), **rank_kw) for k in range(1, args.concurrent_tasks)]
+    if args.concurrent_tasks > 1:
+        if args.augment and args.augment_on_host:   # host pixels are uploaded batch by batch into the main learner: task by task
+            print("--augment-on-host adapts one task at a time: --concurrent-tasks {} is not used.".format(args.concurrent_tasks))
+        else:   # (--augment: model_kwargs gives every lane the batch slots of the device augmenter)
+            lanes = [Learner(device=device, **dict(model_kwargs(args), seed=args.seed + 1000 * k), **rank_kw)
+                     for k in range(1, args.concurrent_tasks)]
+    print("Adapting tasks on {} learner(s).".format(1 + len(lanes)))
 
     if args.restore_efficient_net_weights_from is not None and not args.pretrained:
         path = ckpt.latest_checkpoint(args.restore_efficient_net_weights_from)
