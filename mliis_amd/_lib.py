@@ -126,6 +126,8 @@ SCORE_LIB_PATH = os.path.join(_HERE, "libmliis_score.so")
 SCORE_SIGNATURES = {
     "mliis_score_last_error": (C.c_char_p, []),
     "mliis_mask_iou_counts": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "mliis_mask_pack_words": (_ll, [_i, _i]),
+    "mliis_mask_pack": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 

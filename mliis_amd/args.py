@@ -123,6 +123,13 @@ _EXT = [
     ("--device-metrics", dict(action="store_true", help="score evaluation images on the device (Learner.score_resident: four pixel counts per image come back instead "
                                    "of the prediction mask; the same IoUs bit for bit; its speed against the default host path has not been "
                                    "measured)")),
+    ("--save-predictions", dict(type=str, default=None, metavar="DIR",
+                                help="save every test image's predicted mask of the final evaluation passes as DIR/<task>/sample<k>_query<j>_mask.png "
+                                     "(1-bit PNG; with --device-metrics the mask comes back bit-packed beside the counts).  The environment "
+                                     "variable SAVE_PREDICTIONS (the reference's switch), set to a non-empty string, acts like "
+                                     "--save-predictions predictions --save-prediction-overlays; an explicit DIR wins")),
+    ("--save-prediction-overlays", dict(action="store_true",
+                                        help="with --save-predictions: also save the query image tinted where the mask is set (..._overlay.png)")),
 ]
 
 
@@ -190,6 +197,19 @@ def evaluate_kwargs(a) -> dict:
                 eval_tasks_with_median_early_stopping_iterations=a.eval_tasks_with_median_early_stopping_iterations,
                 save_fine_tuned_checkpoints=a.save_fine_tuned_checkpoints, save_fine_tuned_checkpoints_dir=a.save_fine_tuned_checkpoints_dir,
                 device_metrics=bool(getattr(a, "device_metrics", False)))
+
+
+def prediction_writer(a, environ=None):
+    """The predictions.PredictionWriter of --save-predictions / --save-prediction-overlays / SAVE_PREDICTIONS, or None.  Kept out of
+    evaluate_kwargs: only the final evaluation passes save (not the hyperparameter search, the k-shot curves or meta-training)."""
+    import os
+    directory, overlays = getattr(a, "save_predictions", None), bool(getattr(a, "save_prediction_overlays", False))
+    if (os.environ if environ is None else environ).get("SAVE_PREDICTIONS", ""):   # reptile.py:495-513: the reference's switch and directory
+        directory, overlays = directory or "predictions", True
+    if not directory:
+        return None
+    from .predictions import PredictionWriter
+    return PredictionWriter(directory, overlays=overlays)
 
 
 def hyper_search_kwargs(a) -> dict:

@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import ops, spec
-from ._lib import MliisError, lib
+from ._lib import MliisError, lib, score_lib
 from .arena import Arena
+from .metrics import unpack_mask
 from .passes import _Passes
 from .plan import _Plan
 
@@ -664,6 +665,42 @@ class Learner(_Passes):
             P.counts_pin.copy_(P.counts, non_blocking=True)
         self.stream.synchronize()
         return P.counts_pin.numpy().astype(np.int64)
+
+    def mask_resident(self, idx: Sequence[int], training: bool = False, counts: bool = False, last_only: bool = False):
+        """The prediction masks of predict_resident(idx) -- bool [len(idx), H, W], = predict_resident(idx)[..., 1] > 0.5 -- read back as one
+        bit per pixel (ops.mask_pack on the decoder-resolution logits of score_resident's forward pass; metrics.unpack_mask on the host):
+        H W / 8 bytes per image instead of the 8 H W of the fp32 prediction tensor.  counts=True: (masks, int64 [len(idx), 4]), the rows of
+        score_resident from the same launch.  last_only=True: only the last image of the batch is packed and returned ([1,H,W] / [1,4]) --
+        the per-sample evaluation's "train images + one test image, keep the last"."""
+        idx = [int(i) for i in idx]
+        N = len(idx)
+        if N == 0:
+            raise ValueError("empty batch")
+        lim = self.max_shots + self._aug_valid if self._aug_valid else self.n_shots
+        if min(idx) < 0 or max(idx) >= lim or any(self.n_shots <= i < self.max_shots for i in idx):
+            raise ValueError("image index out of range of the resident task ({} shots)".format(self.n_shots))
+        P = self._plan(N, infer=True)
+        H = self.arch.image_size
+        n0 = N - 1 if last_only else 0
+        with torch.cuda.stream(self.stream):
+            if P.bits is None:
+                words = score_lib.size("mliis_mask_pack_words", H, H)
+                P.bits = torch.zeros((N, words), dtype=torch.int64, device=self.device)
+                P.bits_pin = torch.zeros((N, words), dtype=torch.int64).pin_memory()
+            if counts and P.counts is None:
+                P.counts = torch.zeros((N, 4), dtype=torch.int32, device=self.device)
+                P.counts_pin = torch.zeros((N, 4), dtype=torch.int32).pin_memory()
+            self._upload_idx(P, idx)
+            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            if counts:
+                ops.mask_pack(P.small[n0:], (H, H), self.shots_y, P.idx[n0:], bits=P.bits[n0:], counts=P.counts[n0:])
+                P.counts_pin[n0:].copy_(P.counts[n0:], non_blocking=True)
+            else:
+                ops.mask_pack(P.small[n0:], (H, H), bits=P.bits[n0:])
+            P.bits_pin[n0:].copy_(P.bits[n0:], non_blocking=True)
+        self.stream.synchronize()
+        masks = unpack_mask(P.bits_pin[n0:].numpy(), H, H)
+        return (masks, P.counts_pin[n0:].numpy().astype(np.int64)) if counts else masks
 
     def close(self):
         """Destroy the captured HIP graphs (the buffers themselves are torch tensors and go with the object)."""

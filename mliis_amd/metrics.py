@@ -28,6 +28,20 @@ def iou_from_counts(intersection, union, epsilon: float = 1e-7) -> float:
     return (int(intersection) + epsilon) / (int(union) + epsilon)
 
 
+def unpack_mask(words, H: int, W: int) -> np.ndarray:
+    """bool [..., H, W] from the bit-packed masks of ops.mask_pack (host int64 / uint64 words [..., ceil(H W / 64)]): bit 0 of a word is
+    its first pixel (little-endian bit order, linear over the image); the first H W bits are taken, set bits beyond them ignored."""
+    w = np.ascontiguousarray(words)
+    if w.dtype not in (np.dtype(np.int64), np.dtype(np.uint64)):
+        raise ValueError("unpack_mask: expected int64 / uint64 words, got {}".format(w.dtype))
+    H, W = int(H), int(W)
+    if w.ndim < 1 or w.shape[-1] != (H * W + 63) // 64:
+        raise ValueError("unpack_mask: {} words per image for {} x {} pixels".format(w.shape[-1] if w.ndim else 0, H, W))
+    bytes_ = w.astype("<u8", copy=False).view(np.uint8).reshape(w.shape[:-1] + (w.shape[-1] * 8,))
+    bits = np.unpackbits(bytes_, axis=-1, bitorder="little")[..., :H * W]
+    return bits.astype(bool).reshape(w.shape[:-1] + (H, W))
+
+
 def measure(y_in, pred_in, thresh: float = 0.5):
     y, p = np.asarray(y_in) > thresh, np.asarray(pred_in) > thresh
     return (int((y & p).sum()), int((~y & ~p).sum()), int((~y & p).sum()), int((y & ~p).sum()))

@@ -1237,7 +1237,7 @@ def mask_iou_counts(small, labels, idx, size, counts=None):
     """counts [N,4] int32 = {|P & L|, |P | L|, |P|, |L|} per image: P = the channel-1 prediction mask of resize(small -> size) -> softmax
     > 0.5 (the mask resize_bilinear_fwd -> softmax_ce(want_pred=True) writes, bit for bit), L = round(label channel 1) != 0 of labels
     [S,H,W,2] through idx (nullable).  Neither the full-resolution logits nor the mask are written (metrics.iou_from_counts scores).
-    The one entry point of libmliis_score.so (include/mliis_score.h, csrc/score.hip)."""
+    libmliis_score.so (include/mliis_score.h, csrc/score.hip); mask_pack returns the mask itself beside the counts."""
     N, Hd, Wd, _ = small.shape
     _dense(small, labels, idx, counts)
     H, W = int(size[0]), int(size[1])
@@ -1254,6 +1254,42 @@ def mask_iou_counts(small, labels, idx, size, counts=None):
     _timed("mask_iou_counts", {}, lambda: score_lib.call("mliis_mask_iou_counts", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd, H, W,
                                                    C.c_void_p(counts.data_ptr()), _stream()))
     return counts
+
+
+def mask_pack(small, size, labels=None, idx=None, bits=None, counts=None):
+    """(bits, counts or None): bits [N, words] int64 on the device = the channel-1 prediction mask mask_iou_counts scores, one bit per
+    pixel -- bit l of word w of image n is linear pixel 64 w + l (metrics.unpack_mask reads them back), words = ceil(H W / 64) from the
+    library, tail bits of the last word 0, every word written (bits need not be cleared).  With labels [S,H,W,2] (through idx, nullable):
+    counts [N,4] int32 as well, exactly mask_iou_counts' -- one launch for the score and the mask; without labels idx and counts must be
+    None too and no counts work is done (include/mliis_score.h, csrc/score.hip)."""
+    N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx, bits, counts)
+    H, W = int(size[0]), int(size[1])
+    if small.shape[-1] != 2:
+        raise MliisError("mask_pack: expected small [N,Hd,Wd,2], got {}".format(tuple(small.shape)))
+    if labels is None and (idx is not None or counts is not None):
+        raise MliisError("mask_pack: idx / counts given without labels")
+    if labels is not None:
+        if labels.dim() != 4 or tuple(labels.shape[1:]) != (H, W, 2):
+            raise MliisError("mask_pack: expected labels [S,{},{},2], got {}".format(H, W, tuple(labels.shape)))
+        if idx is not None and (idx.dtype != torch.int32 or idx.numel() != N):
+            raise MliisError("mask_pack: idx must hold {} int32 image indices".format(N))
+        if idx is None and labels.shape[0] < N:
+            raise MliisError("mask_pack: {} label images for {} predictions".format(labels.shape[0], N))
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (N, 4) or not counts.is_cuda):
+            raise MliisError("mask_pack counts: expected a device int32 tensor of shape {}, got {} {}".format((N, 4), tuple(counts.shape), counts.dtype))
+    words = score_lib.size("mliis_mask_pack_words", H, W)
+    if words <= 0:
+        raise MliisError("mask_pack: bad image size {} x {}".format(H, W))
+    if bits is not None and (bits.dtype != torch.int64 or tuple(bits.shape) != (N, words) or not bits.is_cuda):
+        raise MliisError("mask_pack bits: expected a device int64 tensor of shape {}, got {} {}".format((N, words), tuple(bits.shape), bits.dtype))
+    bits = torch.empty((N, words), dtype=torch.int64, device=small.device) if bits is None else bits
+    if labels is not None and counts is None:
+        counts = torch.empty((N, 4), dtype=torch.int32, device=small.device)
+    _timed("mask_pack", {}, lambda: score_lib.call("mliis_mask_pack", _ptr(_chk(small)), _ptr(_chk(labels)) if labels is not None else None, _ptr(idx),
+                                             N, Hd, Wd, H, W, C.c_void_p(bits.data_ptr()), C.c_void_p(counts.data_ptr()) if counts is not None else None,
+                                             _stream()))
+    return bits, counts
 
 
 def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None):

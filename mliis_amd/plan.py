@@ -128,6 +128,8 @@ class _Plan:
         self.head_ws = self.head_fin = None
         # Learner.score_resident: the [N,4] IoU counts on the device and their pinned host copy (allocated by the first scoring call)
         self.counts = self.counts_pin = None
+        # Learner.mask_resident: the [N,words] bit-packed masks on the device and their pinned host copy (allocated by its first call)
+        self.bits = self.bits_pin = None
         # stage-1 BN statistics handed from a producer (GEMM epilogue / stats kernel) to the fused fold+apply kernel
         need = 0
         for b in a.executed():

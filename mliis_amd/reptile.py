@@ -122,13 +122,21 @@ class Gecko:
 
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
-                 aug_pool=None, lanes: Sequence = (), device_metrics: bool = False):
+                 aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None):
         self.learner = learner
         # device_metrics: the evaluation sites score on the device (Learner.score_resident: four integers per image come back) instead of
         # copying every prediction mask to the host for metrics.iou; the same IoUs, bit for bit.  Opt-in; the default path is untouched.
         self.device_metrics = bool(device_metrics)
         if self.device_metrics and not all(callable(getattr(ln, "score_resident", None)) for ln in [learner] + list(lanes)):
             raise ValueError("device_metrics=True needs a learner with score_resident() (the device Learner; the CPU oracle has none)")
+        # prediction_writer (predictions.PredictionWriter): evaluate()'s tasks save every test image's predicted mask (with the writer's
+        # overlays: the query image tinted as well).  With device_metrics the mask comes back bit-packed beside the counts
+        # (Learner.mask_resident); on the default path it is the prediction already on the host.  The IoUs are those of a run without it.
+        self.prediction_writer = prediction_writer
+        if prediction_writer is not None and self.device_metrics and \
+                not all(callable(getattr(ln, "mask_resident", None)) for ln in [learner] + list(lanes)):
+            raise ValueError("device_metrics=True with a prediction writer needs a learner with mask_resident() (the device Learner; the "
+                             "CPU oracle has none)")
         # lanes: further Learners of the same architecture (own arenas, own streams).  The tasks of a meta-batch that fall on this
         # rank are then adapted len(lanes)+1 at a time, their inner steps issued round-robin so the launches of one task fill the
         # compute units the other leaves idle (one 8-image step alone does not fill 256 CUs: profiles/r01_notes.md).  Same update as
@@ -417,7 +425,8 @@ class Gecko:
         ious, task_iou_map = [], {}
         if self._lanes_in_use() and not save_fine_tuned_checkpoints:
             for name, iou in self._evaluate_concurrently(sampled, num_shots, test_shots, inner_batch_size, inner_iters, replacement, lr,
-                                                         drop_rate, self.aug_rate if aug_rate is None else aug_rate):
+                                                         drop_rate, self.aug_rate if aug_rate is None else aug_rate,
+                                                         eval_sample_num=eval_sample_num):
                 ious.append(iou)
                 task_iou_map[name] = iou
             sampled = []
@@ -437,7 +446,7 @@ class Gecko:
         return mean_iou, task_iou_map
 
     def _evaluate_concurrently(self, sampled, num_shots, test_shots, inner_batch_size, inner_iters, replacement, lr, drop_rate,
-                               aug_rate=None):
+                               aug_rate=None, eval_sample_num=None):
         """evaluate's task loop over the lanes: every task of a group is fine-tuned from the same restored state on a learner of
         its own, the steps issued round-robin; host draws (example sampling, mini-batch schedule and, with device augmentation, the
         per-sample recipes) stay in task order and the predictions / IoUs are taken task by task afterwards, so the result equals the
@@ -472,8 +481,10 @@ class Gecko:
                         else:
                             idx = [train_idx[i] for i in schedule[j]]
                         self._fine_tune_step(idx, j, lr, self.lr_scheduler, drop_rate, lane)
-            for lane, name, _, labels, train_idx, test_idx, _ in group:
-                if self.device_metrics:
+            for lane, name, images, labels, train_idx, test_idx, _ in group:
+                if self.prediction_writer is not None:
+                    class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, name, eval_sample_num, images, lane)))
+                elif self.device_metrics:
                     class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane)))
                 else:
                     preds = self._test_predictions(train_idx, test_idx, lane)
@@ -534,7 +545,9 @@ class Gecko:
             save_fine_tuned_checkpoint(L.named_numpy(), save_fine_tuned_checkpoints_dir, task_name, eval_sample_num, inner_iter)
         if self.augmenter is not None and not self.device_aug:
             L.load_task(images, labels)   # the augmented batches replaced the resident task
-        if self.device_metrics:
+        if self.prediction_writer is not None:
+            class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, task_name, eval_sample_num, images)))
+        elif self.device_metrics:
             class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx)))
         else:
             preds = self._test_predictions(train_idx, test_idx)
@@ -710,6 +723,35 @@ class Gecko:
         else:
             rows = [L.score_resident(list(train_idx) + [t], training=False)[-1] for t in test_idx]
         return [iou_from_counts(r[0], r[1]) for r in rows]
+
+    def _ious_saving(self, train_idx, test_idx, labels, task_name, eval_sample_num, images=None, L=None) -> List[float]:
+        """The per-image IoUs of a task's test images -- _device_ious' with device_metrics, _test_predictions + metrics.iou otherwise, over
+        the same batches and to the same floats -- while the prediction writer saves each image's mask: with device_metrics the mask
+        packed by the launch that counts (one mask_resident call in place of each score_resident call), otherwise the channel-1 plane
+        of the prediction already on the host as metrics.iou rounds it."""
+        import numpy as np
+        from .metrics import iou as _iou, iou_from_counts
+        L = L or self.learner
+        if self.device_metrics:
+            if self._transductive:
+                masks, rows = L.mask_resident(list(test_idx), training=False, counts=True)
+            else:
+                masks, rows = [], []
+                for t in test_idx:
+                    m, r = L.mask_resident(list(train_idx) + [t], training=False, counts=True, last_only=True)
+                    masks.append(m[-1])
+                    rows.append(r[-1])
+            ious = [iou_from_counts(r[0], r[1]) for r in rows]
+        else:
+            preds = self._test_predictions(train_idx, test_idx, L)
+            lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+            ious = [_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]
+            masks = [np.round(np.asarray(preds[j])[..., 1]).astype(bool) for j in range(len(test_idx))]
+        W = self.prediction_writer
+        for j, t in enumerate(test_idx):
+            image = _to_numpy(images[t]) if (W.overlays and images is not None) else None
+            W.save(task_name, eval_sample_num, j, masks[j], image=image)
+        return ious
 
 
 class FOMLIS(Gecko):

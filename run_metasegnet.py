@@ -15,6 +15,8 @@ early-stopping harness of the reference + a built-in GP / expected-improvement o
 (mliis_amd/tfrecord.py, no TensorFlow needed) or --synthetic-tasks N.
 --device-metrics: every evaluation (the periodic ones of meta-training, the final passes, the update-hyperparameter search, the k-shot
 curves) scores on the device -- four pixel counts per test image come back instead of its prediction mask; the same IoUs bit for bit.
+--save-predictions DIR [--save-prediction-overlays] (or SAVE_PREDICTIONS=1, the reference's switch): the final evaluation passes save
+every test image's predicted mask as DIR/<task>/sample<k>_query<j>_mask.png (with --device-metrics: one bit per pixel comes back).
 """
 import datetime
 import json
@@ -33,7 +35,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from mliis_amd import checkpoint as ckpt  # noqa: E402
-from mliis_amd.args import argument_parser, augment_mode, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler, model_kwargs, train_kwargs  # noqa: E402
+from mliis_amd.args import (argument_parser, augment_mode, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler, model_kwargs,  # noqa: E402
+                            prediction_writer, train_kwargs)
 
 
 def _dataset(args, device, rank):
@@ -114,18 +117,22 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
                                               k_range=args.k_shot_range, test_samples=args.k_shot_test_samples,
                                               csv_outpath=os.path.join(args.checkpoint, "k-shot-results.csv"), **kk)
         return
+    writer = prediction_writer(args)   # (the final passes only: not the search, the k-shot curves or the training above)
+    if writer is not None:
+        print("Saving predictions to {}".format(writer.directory))
     mean_train_iou = None
     if train_set and not args.skip_train_task_eval:
         print("Evaluating {}-shot learning on training tasks.".format(args.shots))
         keep = ek["save_fine_tuned_checkpoints"]
         ek["save_fine_tuned_checkpoints"] = args.save_fine_tuned_checkpoints_train
-        mean_train_iou, _ = evaluate_gecko(learner, train_set, lr_scheduler=lr_scheduler, serially_eval_all_tasks=False, lanes=lanes, **ek)
+        mean_train_iou, _ = evaluate_gecko(learner, train_set, lr_scheduler=lr_scheduler, serially_eval_all_tasks=False, lanes=lanes,
+                                           prediction_writer=writer, **ek)
         ek["save_fine_tuned_checkpoints"] = keep
     name = "test"
     if args.eval_val_tasks:
         test_set, name = val_set, "val"
     print("Evaluating {}-shot learning on meta-{} tasks.".format(args.shots, name))
-    mean_test_iou, task_name_iou_map = evaluate_gecko(learner, test_set, lr_scheduler=lr_scheduler, lanes=lanes,
+    mean_test_iou, task_name_iou_map = evaluate_gecko(learner, test_set, lr_scheduler=lr_scheduler, lanes=lanes, prediction_writer=writer,
                                                       serially_eval_all_tasks=args.serially_eval_all_test_tasks, **ek)
     print("Evaluated meta-{} tasks:".format(name))
     print(task_name_iou_map)
