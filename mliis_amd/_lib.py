@@ -130,6 +130,13 @@ SCORE_SIGNATURES = {
     "mliis_mask_pack": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
+# libmliis_data.so (include/mliis_data.h): a task's shots expanded / resampled from stored bytes, a library of its own as well
+DATA_LIB_PATH = os.path.join(_HERE, "libmliis_data.so")
+DATA_SIGNATURES = {
+    "mliis_data_last_error": (C.c_char_p, []),
+    "mliis_task_expand_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+}
+
 
 class MliisError(RuntimeError):
     pass
@@ -138,7 +145,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib)."""
+        library of the same conventions (score_lib, data_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -181,3 +188,4 @@ class _Lib:
 
 lib = _Lib()
 score_lib = _Lib(SCORE_LIB_PATH, SCORE_SIGNATURES, "mliis_score_last_error")
+data_lib = _Lib(DATA_LIB_PATH, DATA_SIGNATURES, "mliis_data_last_error")

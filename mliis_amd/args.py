@@ -130,6 +130,13 @@ _EXT = [
                                      "--save-predictions predictions --save-prediction-overlays; an explicit DIR wins")),
     ("--save-prediction-overlays", dict(action="store_true",
                                         help="with --save-predictions: also save the query image tinted where the mask is set (..._overlay.png)")),
+    ("--resident-dataset", dict(action="store_true",
+                                help="keep every task on the device as the bytes the dataset stores (4 per pixel instead of 20 as floats, "
+                                     "metaseg.ByteTask); a task's shots are expanded -- and resampled to --image_size -- on the device "
+                                     "when it becomes resident (csrc/taskload.hip).  Same floats as the default path at the stored size")),
+    ("--stored-image-size", dict(type=int, default=None, metavar="N",
+                                 help="side of the examples the --data-dir shards hold (default: --image_size); another size than "
+                                      "--image_size needs --resident-dataset, which resamples on the device")),
 ]
 
 
@@ -153,6 +160,19 @@ def augment_mode(a):
     if not a.augment:
         return False
     return True if getattr(a, "augment_on_host", False) else "device"
+
+
+def stored_image_size(a) -> int:
+    """The side the shards are parsed at (--stored-image-size, default --image_size); a size other than --image_size is only served by
+    the device resampler of --resident-dataset."""
+    n = getattr(a, "stored_image_size", None)
+    n = a.image_size if n is None else int(n)
+    if n < 1:
+        raise ValueError("--stored-image-size must be positive, got {}".format(n))
+    if n != a.image_size and not getattr(a, "resident_dataset", False):
+        raise ValueError("--stored-image-size {} differs from --image_size {}: the examples are resampled on the device, which needs "
+                         "--resident-dataset".format(n, a.image_size))
+    return n
 
 
 def model_kwargs(a) -> dict:

@@ -373,7 +373,11 @@ class Learner(_Passes):
 
     # ------------------------------------------------------------------------------------------- task data
     def load_task(self, images, labels):
-        """Make a task's shots resident: images [S,H,W,3] f32 0..255, labels [S,H,W,2] (numpy or tensors)."""
+        """Make a task's shots resident: images [S,H,W,3] f32 0..255, labels [S,H,W,2] (numpy or tensors), or the pair of
+        metaseg.ByteViews a ByteTask samples: their bytes are expanded (and resampled to the learner's image size) on the device."""
+        from .metaseg import ByteView
+        if isinstance(images, ByteView) or isinstance(labels, ByteView):
+            return self._load_task_bytes(images, labels)
         images = torch.as_tensor(images)
         labels = torch.as_tensor(labels)
         S = images.shape[0]
@@ -387,6 +391,34 @@ class Learner(_Passes):
         with torch.cuda.stream(self.stream):
             self.shots_x[:S].copy_(images.to(torch.float32), non_blocking=True)
             self.shots_y[:S].copy_(labels.to(torch.float32), non_blocking=True)
+        self.n_shots = S
+        self._aug_valid = 0
+
+    def _load_task_bytes(self, images, labels):
+        """load_task for the (images, labels) ByteViews of one ByteTask: one launch of ops.task_expand_u8 on the learner's stream reads the
+        byte pool and writes shots_x[:S] / shots_y[:S] -- no float copy of the task beside them and, for a pool resident on this device
+        sampled as sample() samples it (its first S examples), no host-to-device traffic at all.  Any other selection uploads its S
+        int32 rows; a pool that lives elsewhere (the host) uploads the selected examples' bytes, 4 per stored pixel."""
+        from .metaseg import ByteView
+        if not (isinstance(images, ByteView) and isinstance(labels, ByteView)) or images.task is not labels.task or images.kind != "x" or \
+                labels.kind != "y" or len(images.shape) != 4 or len(labels.shape) != 4 or not np.array_equal(images.rows, labels.rows):
+            raise ValueError("load_task: byte views come as the (images, labels) pair of one ByteTask over the same examples")
+        task, S, H = images.task, int(images.rows.size), self.arch.image_size
+        if S > self.max_shots:
+            raise ValueError("task has {} shots; Learner was built with max_shots={}".format(S, self.max_shots))
+        if task.image_size != H:
+            raise ValueError("expected images [S,{0},{0},3] and labels [S,{0},{0},2], got {1} / {2}".format(H, images.shape, labels.shape))
+        if S:
+            pool_x, pool_y, idx = task.images_u8, task.masks_u8, None
+            self._in()
+            with torch.cuda.stream(self.stream):
+                if pool_x.device != self.shots_x.device:
+                    rows = images.rows.tolist()
+                    pool_x = pool_x[rows].to(self.shots_x.device, non_blocking=True)
+                    pool_y = pool_y[rows].to(self.shots_x.device, non_blocking=True)
+                elif not images.is_prefix():
+                    idx = torch.from_numpy(images.rows.astype(np.int32)).to(self.shots_x.device, non_blocking=True)
+                ops.task_expand_u8(pool_x, pool_y, idx, self.shots_x[:S], self.shots_y[:S])
         self.n_shots = S
         self._aug_valid = 0
 

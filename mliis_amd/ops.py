@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import MliisError, lib, score_lib
+from ._lib import MliisError, data_lib, lib, score_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1290,6 +1290,37 @@ def mask_pack(small, size, labels=None, idx=None, bits=None, counts=None):
                                              N, Hd, Wd, H, W, C.c_void_p(bits.data_ptr()), C.c_void_p(counts.data_ptr()) if counts is not None else None,
                                              _stream()))
     return bits, counts
+
+
+def task_expand_u8(images_u8, masks_u8, src_idx, x, y):
+    """x [S,H,W,3], y [S,H,W,2] (fp32, written whole) = examples src_idx (device int32 [S]; None = rows 0..S-1) of the byte pool images_u8
+    [n,h,w,3] / masks_u8 [n,h,w], expanded as tfrecord.parse_example expands them (x = float(byte), y = ((255 - m) / 255, m / 255), bit for
+    bit) and, when (h, w) != (H, W), resampled on the way: nearest mask, bilinear image at half-pixel centres (metaseg.expand_bytes_host is
+    the numpy restatement).  One launch, no intermediate tensor.  libmliis_data.so (include/mliis_data.h, csrc/taskload.hip)."""
+    for name, t, dt in (("images_u8", images_u8, torch.uint8), ("masks_u8", masks_u8, torch.uint8), ("x", x, torch.float32), ("y", y, torch.float32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MliisError("task_expand_u8 {}: mliis_amd ops need device tensors (no CPU path)".format(name))
+        if t.dtype != dt:
+            raise MliisError("task_expand_u8 {}: expected {} tensor, got {}".format(name, dt, t.dtype))
+        if t.device != x.device:
+            raise MliisError("task_expand_u8 {}: on {}, x on {}".format(name, t.device, x.device))
+    _dense(images_u8, masks_u8, src_idx, x, y)
+    if images_u8.dim() != 4 or images_u8.shape[-1] != 3 or masks_u8.dim() != 3 or tuple(masks_u8.shape) != tuple(images_u8.shape[:3]):
+        raise MliisError("task_expand_u8: expected images_u8 [n,h,w,3] and masks_u8 [n,h,w], got {} / {}".format(tuple(images_u8.shape),
+                                                                                                           tuple(masks_u8.shape)))
+    if x.dim() != 4 or x.shape[-1] != 3 or y.dim() != 4 or tuple(y.shape) != tuple(x.shape[:3]) + (2,):
+        raise MliisError("task_expand_u8: expected x [S,H,W,3] and y [S,H,W,2], got {} / {}".format(tuple(x.shape), tuple(y.shape)))
+    n, h, w, _ = images_u8.shape
+    S, H, W, _ = x.shape
+    if min(n, h, w, S, H, W) < 1:
+        raise MliisError("task_expand_u8: empty pool or output ({} / {})".format(tuple(images_u8.shape), tuple(x.shape)))
+    if src_idx is not None and (not src_idx.is_cuda or src_idx.device != x.device or src_idx.dtype != torch.int32 or src_idx.numel() != S):
+        raise MliisError("task_expand_u8: src_idx must hold {} int32 pool rows on {}".format(S, x.device))
+    if src_idx is None and n < S:
+        raise MliisError("task_expand_u8: {} examples asked of a pool of {}".format(S, n))
+    _timed("task_expand_u8", {}, lambda: data_lib.call("mliis_task_expand_u8", C.c_void_p(images_u8.data_ptr()), C.c_void_p(masks_u8.data_ptr()),
+                                                       _ptr(src_idx), S, n, h, w, H, W, _ptr(x), _ptr(y), _stream()))
+    return x, y
 
 
 def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None):

@@ -185,11 +185,33 @@ def parse_example(example: bytes, image_width: int = 224) -> Tuple[np.ndarray, n
     return image, label
 
 
+def parse_example_u8(example: bytes, stored_size: int = 224) -> Tuple[np.ndarray, np.ndarray]:
+    """The bytes parse_example expands, as stored: (image uint8 [h,h,3], mask uint8 [h,h]) with h = stored_size (views of the record)."""
+    f = parse_example_bytes(example)
+    if "image" not in f or "mask" not in f:
+        raise ValueError("example lacks the 'image' / 'mask' features")
+    img = np.frombuffer(f["image"], dtype=np.uint8)
+    msk = np.frombuffer(f["mask"], dtype=np.uint8)
+    if img.size != stored_size * stored_size * 3 or msk.size != stored_size * stored_size:
+        raise ValueError("example is not {0}x{0}: image {1} bytes, mask {2} bytes".format(stored_size, img.size, msk.size))
+    return img.reshape(stored_size, stored_size, 3), msk.reshape(stored_size, stored_size)
+
+
 class ShardTask:
     """One binary segmentation task = one shard (meta_learners/metaseg.py:181-230).  Examples are decoded once, lazily."""
 
-    def __init__(self, path, image_size: int = 224, name: Optional[str] = None):
-        """`path`: one shard, or a list of shards read one after another (the FP-k tasks pool the shards of several synonyms)."""
+    def __init__(self, path, image_size: int = 224, name: Optional[str] = None, resident=None, stored_size: Optional[int] = None):
+        """`path`: one shard, or a list of shards read one after another (the FP-k tasks pool the shards of several synonyms).
+        `resident` (a torch device, or "cpu"): the task keeps the shard's BYTES there (metaseg.ByteTask) and sample() hands out byte views
+        that expand -- and resample from `stored_size` (default image_size) to image_size -- where they are used; on first use the
+        bytes go up once and the upload is waited for, so that any stream may read them afterwards.  Default (None): host float arrays
+        at image_size, as the reference's reader makes them."""
+        self.resident = resident
+        self.stored_size = int(image_size if stored_size is None else stored_size)
+        if resident is None and self.stored_size != image_size:
+            raise ValueError("shards stored at {0}x{0} cannot be read at image size {1} on the host: the resampling runs on the device "
+                             "(--resident-dataset)".format(self.stored_size, image_size))
+        self._bytes = None
         self.tfrecord_paths = path
         self._paths = [path] if isinstance(path, str) else list(path)
         self.name = name or os.path.basename(self._paths[0])
@@ -203,10 +225,25 @@ class ShardTask:
             self._images = np.stack([p[0] for p in pairs])
             self._labels = np.stack([p[1] for p in pairs])
 
+    def _load_bytes(self):
+        if self._bytes is None:
+            import torch
+            from .metaseg import ByteTask
+            pairs = [parse_example_u8(r, self.stored_size) for p in self._paths for r in read_records(p)]
+            images, masks = torch.from_numpy(np.stack([p[0] for p in pairs])), torch.from_numpy(np.stack([p[1] for p in pairs]))
+            device = torch.device(self.resident)
+            if device.type != "cpu":
+                images, masks = images.to(device), masks.to(device)
+                torch.cuda.synchronize(device)   # uploaded once, and waited for HERE: every later reader, on any stream, finds it complete
+            self._bytes = ByteTask(self.name, images, masks, self.image_size)
+        return self._bytes
+
     def sample(self, num_images: int):
         if num_images > self.batch_size:
             raise ValueError("Tried to sample {} examples.Cannot sample more than {} examples that generator was initialized with.".format(
                 num_images, self.batch_size))
+        if self.resident is not None:
+            return self._load_bytes().sample(num_images)
         self._load()
         return self._images[:num_images], self._labels[:num_images]
 
@@ -235,8 +272,9 @@ def split_train_test_tasks(all_tasks: List[str], n_test: int, reproducible_split
 
 
 def read_fss_1000_dataset(data_dir: str, num_val_tasks: int = 0, num_test_tasks: int = 240, test_task_ids: Optional[List[str]] = "fss",
-                          image_size: int = 224):
-    """(train_tasks, val_tasks, test_tasks, train_names, val_names, test_names) -- meta_learners/metaseg.py:24-121."""
+                          image_size: int = 224, resident=None, stored_size: Optional[int] = None):
+    """(train_tasks, val_tasks, test_tasks, train_names, val_names, test_names) -- meta_learners/metaseg.py:24-121.
+    resident / stored_size: ShardTask's (the tasks keep their bytes on that device; shards stored at another size than image_size)."""
     if test_task_ids == "fss":
         test_task_ids = fss_test_task_ids()
     shards = glob.glob(os.path.join(data_dir, "*.tfrecord*"))
@@ -249,7 +287,7 @@ def read_fss_1000_dataset(data_dir: str, num_val_tasks: int = 0, num_test_tasks:
         train_shards = [p for p in shards if key(p) not in ids]
     train_shards, val_shards = split_train_test_tasks(train_shards, num_val_tasks, reproducible_splits=True)
     print("{} training tasks, {} val tasks, {} test tasks.".format(len(train_shards), len(val_shards), len(test_shards)))
-    mk = lambda ps: [ShardTask(p, image_size) for p in ps]  # noqa: E731
+    mk = lambda ps: [ShardTask(p, image_size, resident=resident, stored_size=stored_size) for p in ps]  # noqa: E731
     tr, va, te = mk(train_shards), mk(val_shards), mk(test_shards)
     return tr, va, te, [t.name for t in tr], [t.name for t in va], [t.name for t in te]
 
@@ -257,7 +295,8 @@ def read_fss_1000_dataset(data_dir: str, num_val_tasks: int = 0, num_test_tasks:
 DEFAULT_K_SHOT_SET = [{"airliner", "aeroplane"}, {"bus"}, {"motorbike"}, {"potted_plant", "potted plant"}, {"television", "tvmonitor"}]
 
 
-def read_fp_k_shot_dataset(data_dir: str, all_task_names=DEFAULT_K_SHOT_SET, image_size: int = 224):
+def read_fp_k_shot_dataset(data_dir: str, all_task_names=DEFAULT_K_SHOT_SET, image_size: int = 224, resident=None,
+                           stored_size: Optional[int] = None):
     """(tasks, task names) of the FP-k-shot set -- meta_learners/metaseg.py:124-179: one task per synonym set, pooling every shard
     whose file name contains one of the synonyms (blanks removed); the task is named after the first synonym the set iterates to
     (Python set order, as in the reference).  Shards are read in sorted-path order (the reference hands TensorFlow a list of globs)."""
@@ -276,7 +315,7 @@ def read_fp_k_shot_dataset(data_dir: str, all_task_names=DEFAULT_K_SHOT_SET, ima
         print("task shards: {}".format(shards))
         if not shards:
             raise ValueError("no shards for task {} under {}".format(task_name, data_dir))
-        t = ShardTask(shards, image_size, name=task_name)
+        t = ShardTask(shards, image_size, name=task_name, resident=resident, stored_size=stored_size)
         print("{} examples in task {}".format(t.batch_size, task_name))
         tasks.append(t)
         names.append(task_name)

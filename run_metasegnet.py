@@ -17,6 +17,9 @@ early-stopping harness of the reference + a built-in GP / expected-improvement o
 curves) scores on the device -- four pixel counts per test image come back instead of its prediction mask; the same IoUs bit for bit.
 --save-predictions DIR [--save-prediction-overlays] (or SAVE_PREDICTIONS=1, the reference's switch): the final evaluation passes save
 every test image's predicted mask as DIR/<task>/sample<k>_query<j>_mask.png (with --device-metrics: one bit per pixel comes back).
+--resident-dataset: the tasks stay on the device as the bytes the dataset stores (4 per pixel, not 20); a task's shots are expanded on
+the device when it becomes resident (csrc/taskload.hip) -- and resampled to --image_size when the shards hold another size
+(--stored-image-size N).
 """
 import datetime
 import json
@@ -36,28 +39,34 @@ if ROOT not in sys.path:
 
 from mliis_amd import checkpoint as ckpt  # noqa: E402
 from mliis_amd.args import (argument_parser, augment_mode, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler, model_kwargs,  # noqa: E402
-                            prediction_writer, train_kwargs)
+                            prediction_writer, stored_image_size, train_kwargs)
 
 
 def _dataset(args, device, rank):
     """(train, val, test) task lists (run_metasegnet.py:79-98); val is None when empty."""
-    from mliis_amd.metaseg import DeviceTask, synthetic_task
+    from mliis_amd.metaseg import ByteTask, DeviceTask, synthetic_task, synthetic_task_bytes
+    stored = stored_image_size(args)   # (refuses a stored size other than --image_size without --resident-dataset)
     if not args.synthetic_tasks:
         if not args.data_dir:
             raise SystemExit("pass --data-dir <FSS-1000 TFRecord-GZIP shards> or --synthetic-tasks N")
         from mliis_amd import tfrecord
+        byte_kw = dict(resident=device, stored_size=stored) if args.resident_dataset else {}   # the tasks keep the shards' bytes on the device
         if args.run_k_shot_learning_curves_experiment:
-            test, _ = tfrecord.read_fp_k_shot_dataset(args.data_dir, image_size=args.image_size)
+            test, _ = tfrecord.read_fp_k_shot_dataset(args.data_dir, image_size=args.image_size, **byte_kw)
             return None, None, test
         ids = tfrecord.fp_k_test_task_ids() if args.fp_k_test_set else "fss"
         train, val, test, _, _, _ = tfrecord.read_fss_1000_dataset(args.data_dir, num_val_tasks=args.num_val_tasks, test_task_ids=ids,
-                                                                   image_size=args.image_size)
+                                                                   image_size=args.image_size, **byte_kw)
         return train, (val or None), test
     n_ex = max(args.train_shots or 0, args.shots + 5)
     if args.run_k_shot_learning_curves_experiment:
         n_ex = max(n_ex, max(args.k_shot_range or [400]) + args.k_shot_test_samples)
     tasks = []
     for i in range(args.synthetic_tasks):
+        if args.resident_dataset:   # the same tasks as the bytes they are drawn as (made at the stored size): they expand to the same floats
+            xb, mb = synthetic_task_bytes(n_ex, stored, seed=i)
+            tasks.append(ByteTask("synthetic_{:04d}".format(i), torch.from_numpy(xb).to(device), torch.from_numpy(mb).to(device), args.image_size))
+            continue
         x, y = synthetic_task(n_ex, args.image_size, seed=i)
         tasks.append(DeviceTask("synthetic_{:04d}".format(i), torch.from_numpy(x).to(device), torch.from_numpy(y).to(device)))
     n_test = max(1, len(tasks) // 4)
@@ -152,6 +161,7 @@ def main(argv=None, learner_factory=None, device=None):
     start = datetime.datetime.now()
     print("Experiment started at: {}".format(start))
     args = argument_parser().parse_args(argv)
+    stored_image_size(args)   # (a stored size other than --image_size without --resident-dataset is refused before anything is built)
     random.seed(args.seed)
     aug_pool = None
     if args.augment and args.augment_on_host and args.augment_workers != 0:   # forked workers: created before anything initialises the GPU
