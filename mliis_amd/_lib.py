@@ -137,6 +137,15 @@ DATA_SIGNATURES = {
     "mliis_task_expand_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
+# libmliis_steplog.so (include/mliis_steplog.h): the inner loop's step log, a library of its own as well
+STEPLOG_LIB_PATH = os.path.join(_HERE, "libmliis_steplog.so")
+STEPLOG_SIGNATURES = {
+    "mliis_steplog_last_error": (C.c_char_p, []),
+    "mliis_steplog_workspace_bytes": (_sz, []),
+    "mliis_steplog_record_words": (_i, []),
+    "mliis_steplog_append": (_i, [_p, _p, _p, _p, _ll, _p, _p, _i, _p, _p]),
+}
+
 
 class MliisError(RuntimeError):
     pass
@@ -145,7 +154,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib, data_lib)."""
+        library of the same conventions (score_lib, data_lib, steplog_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -189,3 +198,4 @@ class _Lib:
 lib = _Lib()
 score_lib = _Lib(SCORE_LIB_PATH, SCORE_SIGNATURES, "mliis_score_last_error")
 data_lib = _Lib(DATA_LIB_PATH, DATA_SIGNATURES, "mliis_data_last_error")
+steplog_lib = _Lib(STEPLOG_LIB_PATH, STEPLOG_SIGNATURES, "mliis_steplog_last_error")

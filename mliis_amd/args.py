@@ -9,6 +9,7 @@ import argparse
 from functools import partial
 
 from .lr_schedulers import supported_learning_rate_schedulers
+from .steplog import capacity_for
 
 SUPPORTED_MODELS = {"efficientlab"}
 SUPPORTED_SEARCH_ALGS = {"GP"}
@@ -137,6 +138,16 @@ _EXT = [
     ("--stored-image-size", dict(type=int, default=None, metavar="N",
                                  help="side of the examples the --data-dir shards hold (default: --image_size); another size than "
                                       "--image_size needs --resident-dataset, which resamples on the device")),
+    ("--inner-loop-log", dict(action="store_true",
+                              help="log the inner loop: every training step appends its loss, IoU, learning rate, gradient norm and the "
+                                   "non-finite counts of gradient and parameters to a ring on the device (csrc/steplog.hip: one more launch "
+                                   "in the step's graph, no host round trip per step); once per meta-iteration the ring is read and one "
+                                   "summary line goes to <checkpoint>/train/inner_loop.jsonl")),
+    ("--on-divergence", dict(choices=["off", "skip", "abort"], default="off",
+                             help="what a non-finite loss, gradient or parameter in an inner step of any rank does to the meta-update: "
+                                  "off = nothing (logged with --inner-loop-log), skip = the meta-iteration's update is left out on all "
+                                  "ranks, abort = stop with an error before the update and before any checkpoint is written; skip and "
+                                  "abort imply --inner-loop-log")),
 ]
 
 
@@ -175,11 +186,21 @@ def stored_image_size(a) -> int:
     return n
 
 
+def inner_loop_log(a) -> bool:
+    """--inner-loop-log, or an --on-divergence that needs it."""
+    return bool(getattr(a, "inner_loop_log", False)) or getattr(a, "on_divergence", "off") != "off"
+
+
 def model_kwargs(a) -> dict:
     """Keyword arguments of mliis_amd.learner.Learner from parsed flags (reference: args.py:121-160)."""
     a.model_name = a.model_name.lower()
     if a.model_name not in SUPPORTED_MODELS:
         raise ValueError("Model name must be in the set: {} but is {}".format(SUPPORTED_MODELS, a.model_name))
+    # (the step log's ring holds the steps of one task; the key is absent without the flags: the learner is built as always)
+    steps = a.inner_iters
+    if getattr(a, "meta_fine_tune_steps_on_train_val", 0) > 0:   # (that phase adapts with the searched step count, two steps per batch)
+        steps = max(steps, 2 * a.max_steps)
+    log = dict(step_log=capacity_for(steps)) if inner_loop_log(a) else {}
     return dict(feature_extractor_name=a.feature_extractor_name, image_size=a.image_size, rsd=a.rsd or None,
                 learning_rate=a.learning_rate, optimizer="sgd" if a.sgd else "adam", l2=a.l2, l1=a.l1, darc1=a.darc1,
                 dice=("dice" in a.loss_name), label_smoothing=a.label_smoothing, final_layer_dropout_rate=a.final_layer_dropout_rate,
@@ -187,7 +208,7 @@ def model_kwargs(a) -> dict:
                 use_graph=not getattr(a, "no_hip_graph", False), max_shots=_max_shots(a),
                 matmul_precision=getattr(a, "matmul_precision", "fp32"),
                 augment_batch_capacity=(max(16, a.inner_batch, a.eval_batch, getattr(a, "batch_size_search_range_high", 0) or 0)
-                                        if augment_mode(a) == "device" else 0))
+                                        if augment_mode(a) == "device" else 0), **log)
     # --disable_rsd_residual_connections is a no-op in the reference too (kwarg name mismatch)
 
 
@@ -207,7 +228,8 @@ def train_kwargs(a) -> dict:
                 inner_iters=a.inner_iters, replacement=a.replacement, meta_step_size=a.meta_step, meta_step_size_final=a.meta_step_final,
                 meta_batch_size=a.meta_batch, meta_iters=a.meta_iters, eval_inner_batch_size=a.eval_batch, eval_inner_iters=a.eval_iters,
                 eval_interval=a.eval_interval, weight_decay_rate=a.weight_decay, transductive=a.transductive, meta_fn=_meta_fn(a),
-                aug_rate=a.aug_rate, device_metrics=bool(getattr(a, "device_metrics", False)))
+                aug_rate=a.aug_rate, device_metrics=bool(getattr(a, "device_metrics", False)),
+                **(dict(inner_loop_log=True, on_divergence=a.on_divergence) if inner_loop_log(a) else {}))
 
 
 def evaluate_kwargs(a) -> dict:

@@ -29,11 +29,12 @@ import numpy as np
 import torch
 
 from . import ops, spec
-from ._lib import MliisError, lib, score_lib
+from ._lib import MliisError, lib, score_lib, steplog_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
 from .plan import _Plan
+from .steplog import decode as decode_step_log
 
 
 class Learner(_Passes):
@@ -43,7 +44,7 @@ class Learner(_Passes):
                  spatial_pyramid_pooling: bool = False, skip_decoding: bool = False, drop_connect: bool = True, seed: int = 0,
                  device="cuda:0", use_graph: bool = True, max_shots: int = 16, matmul_precision: str = "fp32",
                  small_fused: Optional[bool] = None, dw_march: Optional[bool] = None, fuse_bn2: Optional[bool] = None, fuse_head: Optional[bool] = None,
-                 augment_batch_capacity: int = 0, rng_stream: int = 0):
+                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam' (Adam with beta1=0, the reference default)")
         if not torch.cuda.is_available():
@@ -130,6 +131,23 @@ class Learner(_Passes):
         self.adam_t = torch.zeros(1, dtype=torch.float32, device=self.device)          # Adam steps applied so far
         self.adam_ticket = torch.zeros(1, dtype=torch.int32, device=self.device)   # the optimizer launch advances adam_t itself
         self.adam_epoch = 0     # bumped whenever the Adam slots are REPLACED from outside (restore / import_all): lanes follow (reptile.py)
+        # step_log = CAPACITY > 0: every training step ends with one more launch (ops.steplog_append, captured into the step's graph like the
+        # rest) that appends a record of the step -- loss / ce / iou, the rate, the gradient's norm and largest magnitude, the non-finite
+        # counts of gradient and parameters -- to a ring of CAPACITY records in device memory; read_step_log() fetches them.  Fixed at
+        # construction; 0 (the default): no buffer exists and the step issues exactly the launches it always did.
+        self.step_log = int(step_log)
+        if self.step_log < 0:
+            raise ValueError("step_log is a ring capacity: 0 (off) or a positive number of records, got {}".format(step_log))
+        self._log_ring = self._log_cursor = self._log_ws = self._log_pin = None
+        self._log_seen = 0      # the device cursor at the last read_step_log() (or skip_step_log())
+        self._log_issued = 0    # steps issued since construction: what the device cursor reaches once the stream has drained
+        if self.step_log:
+            steplog_lib.load()  # (a missing library is an error here, not at the first step)
+            words = steplog_lib.size("mliis_steplog_record_words")
+            self._log_ring = torch.zeros((self.step_log, words), dtype=torch.int32, device=self.device)
+            self._log_cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._log_ws = ops.steplog_workspace(self.device)
+            self._log_pin = torch.zeros(self.step_log * words + 1, dtype=torch.int32).pin_memory()
         self.plans: Dict[object, _Plan] = {}   # key: batch size (training plan) or (batch size, "infer") in bf16-storage mode
         self.max_shots = max_shots
         H = image_size
@@ -545,6 +563,8 @@ class Learner(_Passes):
                 ops.darc1(logits, spec.L2_WEIGHT, dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
         self._backward(P, self.shots_x, P.idx, head_fused=head_fused)
         self._apply()
+        if self.step_log:   # the step's record: P.loss_out is final here, arena.grad is what _apply() consumed, theta what it left
+            ops.steplog_append(P.loss_out, self.lr_dev, self.arena.grad, self.arena.theta, self._log_ws, self._log_cursor, out=self._log_ring)
 
     def _upload_idx(self, P: _Plan, idx: Sequence[int]):
         """A batch's image indices into P.idx through the ring of pinned slots (call on the learner's stream): inner_step's upload, for
@@ -614,8 +634,38 @@ class Learner(_Passes):
             else:
                 self._train_sequence(P, draw)
             P.steps_run += 1
+        if self.step_log:
+            self._log_issued += 1
         self.last_loss = P.loss_out
         return P.loss_out
+
+    # ------------------------------------------------------------------------------------------- step log
+    def read_step_log(self):
+        """(records, dropped): the records of the inner steps taken since the last call (or skip_step_log()), in step order, as a
+        steplog.RECORD_DTYPE array, and the number of steps whose records the ring no longer held -- more steps ran than step_log records
+        fit, and the oldest were overwritten.  Waits for the learner's stream; ring and cursor come back through pinned memory in one
+        copy each.  This is the only host synchronisation the log costs: the steps themselves append on the device."""
+        if not self.step_log:
+            raise MliisError("this Learner was built without a step log (step_log=0)")
+        n = self._log_ring.numel()
+        with torch.cuda.stream(self.stream):
+            self._log_pin[:n].copy_(self._log_ring.view(-1), non_blocking=True)
+            self._log_pin[n:].copy_(self._log_cursor, non_blocking=True)
+        self.stream.synchronize()
+        host = self._log_pin.numpy()
+        cursor = int(host[n]) & 0xFFFFFFFF
+        records, dropped = decode_step_log(host[:n].reshape(self.step_log, -1), cursor, self._log_seen)
+        self._log_seen = cursor
+        return records, dropped
+
+    def step_log_pending(self) -> int:
+        """Steps issued since the last read_step_log() / skip_step_log() (host count: nothing is read from the device)."""
+        return (self._log_issued - self._log_seen) & 0xFFFFFFFF
+
+    def skip_step_log(self):
+        """Forget the records of the steps issued so far without reading them (no synchronisation): the next read_step_log() starts behind
+        them."""
+        self._log_seen = self._log_issued & 0xFFFFFFFF
 
     def _fill_masks(self, P: _Plan, dc_scales, dropout_mask, drop_rate=None, aspp_masks=None) -> bool:
         """Masks handed in by the caller (parity tests) are copied into the plan's buffers; returns True when the step has to draw its

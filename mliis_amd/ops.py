@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import MliisError, data_lib, lib, score_lib
+from ._lib import MliisError, data_lib, lib, score_lib, steplog_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1321,6 +1321,54 @@ def task_expand_u8(images_u8, masks_u8, src_idx, x, y):
     _timed("task_expand_u8", {}, lambda: data_lib.call("mliis_task_expand_u8", C.c_void_p(images_u8.data_ptr()), C.c_void_p(masks_u8.data_ptr()),
                                                        _ptr(src_idx), S, n, h, w, H, W, _ptr(x), _ptr(y), _stream()))
     return x, y
+
+
+def steplog_workspace(device) -> torch.Tensor:
+    """The zeroed workspace of one step log (int32 words; the size is the library's): it holds the launch's arrival counter, which must be
+    zero before the first steplog_append and is left at zero by every one."""
+    return torch.zeros(steplog_lib.size("mliis_steplog_workspace_bytes") // 4, dtype=torch.int32, device=device)
+
+
+def steplog_append(loss4, lr_dev, grad, theta, ws, cursor, out=None, capacity=None):
+    """Append one record of a training step to the ring `out` (device int32 [capacity, 8]; allocated zeroed when None, `capacity` rows):
+    words {loss, ce, iou (loss4[0..2], bit for bit), lr (*lr_dev), grad_l2, grad_absmax (over the finite elements of grad; fp32 bits),
+    grad_nonfinite, theta_nonfinite (uint32 counts)} -- steplog.RECORD_DTYPE reads them.  The row is ring[cursor % capacity], cursor a
+    device int32 [1] the launch reads and advances itself, so the call can be captured into a HIP graph and replayed.  grad / theta: the
+    packed fp32 arenas (same length, a multiple of 4, read only); ws: steplog_workspace().  One launch on the current stream.
+    libmliis_steplog.so (include/mliis_steplog.h, csrc/steplog.hip)."""
+    for name, t, dt in (("loss4", loss4, torch.float32), ("lr_dev", lr_dev, torch.float32), ("grad", grad, torch.float32),
+                        ("theta", theta, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MliisError("steplog_append {}: mliis_amd ops need device tensors (no CPU path)".format(name))
+        if dt is not None and t.dtype != dt:
+            raise MliisError("steplog_append {}: expected {} tensor, got {}".format(name, dt, t.dtype))
+        if t.device != grad.device:
+            raise MliisError("steplog_append {}: on {}, grad on {}".format(name, t.device, grad.device))
+    _dense(loss4, lr_dev, grad, theta, ws, cursor, out)
+    if loss4.numel() < 3 or lr_dev.numel() < 1 or cursor.numel() != 1:
+        raise MliisError("steplog_append: loss4 holds at least 3 floats, lr_dev one float and cursor one int32 (got {} / {} / {})".format(
+            loss4.numel(), lr_dev.numel(), cursor.numel()))
+    if grad.numel() != theta.numel():
+        raise MliisError("steplog_append: grad has {} elements, theta {}".format(grad.numel(), theta.numel()))
+    need = steplog_lib.size("mliis_steplog_workspace_bytes")
+    if ws.element_size() != 4 or ws.numel() * 4 < need:
+        raise MliisError("steplog_append ws: {} bytes of 32-bit words needed (steplog_workspace), got {} x {} bytes".format(need, ws.numel(),
+                                                                                                                      ws.element_size()))
+    words = steplog_lib.size("mliis_steplog_record_words")
+    if out is None:
+        if capacity is None or int(capacity) < 1:
+            raise MliisError("steplog_append: capacity = {!r} (a ring of at least one record, or out=)".format(capacity))
+        out = torch.zeros((int(capacity), words), dtype=torch.int32, device=grad.device)
+    else:
+        if not torch.is_tensor(out) or not out.is_cuda or out.device != grad.device or out.dtype != torch.int32 or out.dim() != 2 or \
+                out.shape[1] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
+            raise MliisError("steplog_append out: expected a device int32 ring of shape ({}, {}), got {} {}".format(
+                "capacity" if capacity is None else int(capacity), words, tuple(out.shape) if torch.is_tensor(out) else out,
+                out.dtype if torch.is_tensor(out) else type(out)))
+    _timed("steplog_append", {}, lambda: steplog_lib.call("mliis_steplog_append", _ptr(loss4), _ptr(lr_dev), _ptr(grad), _ptr(theta),
+                                                          grad.numel(), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                          int(out.shape[0]), C.c_void_p(cursor.data_ptr()), _stream()))
+    return out
 
 
 def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None):

@@ -25,6 +25,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import metaseg
+from . import steplog
 from .spec import BN_MOMENTUM
 
 
@@ -122,8 +123,26 @@ class Gecko:
 
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
-                 aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None):
+                 aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None, step_log: bool = False,
+                 on_divergence: str = "off"):
         self.learner = learner
+        # step_log: the learner and every lane were built with a step log (Learner(step_log=CAPACITY)); after the task loop of a
+        # meta-batch and BEFORE its all-reduce their rings are read, the records attributed to tasks by issue order and condensed into
+        # one row (steplog.summarize: inner_loop_summary, handed to inner_loop_sink when one is set).  on_divergence: what a non-finite
+        # loss, gradient or parameter in any inner step of any rank does to the meta-update -- "off" logs it, "skip" leaves the update out
+        # on all ranks, "abort" raises steplog.DivergenceError before the update; anything but "off" needs the log.  Opt-in; the default
+        # path is untouched.
+        if on_divergence not in steplog.ON_DIVERGENCE:
+            raise ValueError("on_divergence must be one of {}, got {!r}".format(steplog.ON_DIVERGENCE, on_divergence))
+        self.on_divergence = on_divergence
+        self.step_log = bool(step_log) or on_divergence != "off"
+        if self.step_log and not all(callable(getattr(ln, "read_step_log", None)) and int(getattr(ln, "step_log", 0)) > 0
+                                     for ln in [learner] + list(lanes)):
+            raise ValueError("step_log=True / on_divergence={!r} need a learner (and lanes) built with a step log "
+                             "(Learner(step_log=CAPACITY))".format(on_divergence))
+        self.inner_loop_summary = None   # the row of the last meta-iteration
+        self.inner_loop_sink = None      # callable(row): train_gecko's writer of inner_loop.jsonl
+        self.skipped_meta_iters = 0
         # device_metrics: the evaluation sites score on the device (Learner.score_resident: four integers per image come back) instead of
         # copying every prediction mask to the host for metrics.iou; the same IoUs, bit for bit.  Opt-in; the default path is untouched.
         self.device_metrics = bool(device_metrics)
@@ -271,6 +290,7 @@ class Gecko:
             # pool while the device trains on the earlier ones.
             mine = [t for t in range(meta_batch_size) if self.rng_mode == "reference" or t % D.world == D.rank]
             ahead = {}
+            adam0 = self._log_begin() if self.step_log else None
             if self.augmenter is not None and not self.device_aug:
                 for t in mine:
                     rng = self._rng(t)
@@ -293,6 +313,8 @@ class Gecko:
                     batches = ahead.pop(t).batches()
                 L.import_bn(self._bn_zero)
                 last_backup = None
+                if self.step_log:
+                    self._log_task(L, t, T)
                 for j, idx in enumerate(batches):
                     if fomaml and j == inner_iters - 1:
                         last_backup = L.export_trainable()
@@ -307,6 +329,16 @@ class Gecko:
                 L.axpby(-1.0, last_backup if fomaml else old, 1.0, delta)
                 L.axpby(decay ** ((meta_batch_size - 1 - t) * T), L.export_bn(), 1.0, bn_acc)
                 L.import_trainable(old)
+            if self.step_log:
+                try:
+                    skip = self._log_guard(T, adam0)
+                except steplog.DivergenceError:   # "abort": the learner is left as it was before this meta-iteration
+                    L.import_bn(bn0)
+                    raise
+                if skip:   # no all-reduce and no update on any rank; the iteration still counts
+                    L.import_bn(bn0)
+                    self.meta_iter += 1
+                    return
             D.all_reduce_sum(comm)
             # theta <- old + (eps / B) * sum_t delta_t ;  bn <- decay^(B*T) * bn0 + sum_t decay^((B-1-t)T) S_t
             L.axpby(meta_step_size / meta_batch_size, delta, 1.0, old)
@@ -341,6 +373,8 @@ class Gecko:
                 if lane is not L:
                     lane.import_trainable(old)
                 lane.import_bn(self._bn_zero)
+                if self.step_log:
+                    self._log_task(lane, t, T)
                 group.append([lane, t, list(batches), None])
             for j in range(max(len(g[2]) for g in group)):
                 for g in group:
@@ -357,6 +391,73 @@ class Gecko:
                 L.axpby(-1.0, last_backup if fomaml else old, 1.0, delta)
                 L.axpby(decay ** ((meta_batch_size - 1 - t) * T), lane.export_bn(), 1.0, bn_acc)
             L.import_trainable(old)
+
+    # ------------------------------------------------------------------------------------------------ inner-loop log
+    def _log_begin(self):
+        """Start a meta-batch's log: records of steps taken since the last one (evaluation fine-tunes on the same learners) are forgotten.
+        Returns, for on_divergence="skip" with Adam, the optimizer slots of every learner as they are now (a skipped iteration puts them
+        back: a non-finite gradient has gone into the second moments)."""
+        learners = [self.learner] + (self.lanes if self._lanes_in_use() else [])
+        self._log_state = {id(ln): [ln, [], [], 0] for ln in learners}   # learner, its task indices, (records, dropped) chunks, pending
+        for ln in learners:
+            skip = getattr(ln, "skip_step_log", None)
+            if skip is not None:
+                skip()
+            else:
+                ln.read_step_log()
+        if self.on_divergence != "skip":
+            return None
+        saved = []
+        for ln in learners:
+            if getattr(ln, "adam_v", None) is not None:
+                with torch.cuda.stream(ln.stream):
+                    saved.append((ln, ln.adam_v.clone(), ln.adam_t.clone()))
+        return saved
+
+    def _log_task(self, lane, t: int, T: int):
+        """Task t's T steps are about to be issued on `lane`: its records are the next T of that learner's log.  A ring that could not
+        hold them beside the ones still unread is read first."""
+        st = self._log_state[id(lane)]
+        if T > int(lane.step_log):
+            raise ValueError("a task takes {} inner steps but the learner's step log holds {} records".format(T, lane.step_log))
+        if st[3] + T > int(lane.step_log):
+            st[2].append(lane.read_step_log())
+            st[3] = 0
+        st[1].append(t)
+        st[3] += T
+
+    def _log_guard(self, T: int, adam0) -> bool:
+        """Read every learner's ring, build the meta-iteration's row and apply on_divergence.  True: the meta-update is to be skipped (on
+        every rank: the flag is a collective OR)."""
+        import numpy as np
+        L, D = self.learner, self.dist
+        tasks = []
+        for ln, ts, chunks, _ in self._log_state.values():
+            chunks = chunks + [ln.read_step_log()]
+            records = np.concatenate([c[0] for c in chunks])
+            tasks += list(zip(ts, steplog.split_tasks(records, T, len(ts), sum(c[1] for c in chunks))))
+        row = steplog.summarize(tasks, self.meta_iter)
+        bad = row["nonfinite_steps"] > 0
+        if self.on_divergence != "off":   # the ranks must take the same branch, or the next all-reduce hangs
+            bad = D.any_true(bad, device=getattr(L, "device", None))
+        skip = bad and self.on_divergence == "skip"
+        row["skipped"] = bool(skip)
+        self.inner_loop_summary = row
+        if self.inner_loop_sink is not None:
+            self.inner_loop_sink(row)
+        first = row["first_nonfinite"] or {}
+        if bad and self.on_divergence == "abort":
+            raise steplog.DivergenceError(self.meta_iter, first.get("task"), first.get("step"), D.rank)
+        if skip:
+            self.skipped_meta_iters += 1
+            for ln, v, t in adam0 or []:
+                with torch.cuda.stream(ln.stream):
+                    ln.adam_v.copy_(v)
+                    ln.adam_t.copy_(t)
+            if D.rank == 0:
+                where = "task {} step {}".format(first["task"], first["step"]) if first else "a task of another rank"
+                print("Meta-iteration {} skipped: non-finite inner step at {}.".format(self.meta_iter, where))
+        return bool(skip)
 
     def _sync_lane_optimizer_state(self):
         """Adam only: after the main learner's slots were replaced from outside (load_named / import_all) copy them into every lane."""
