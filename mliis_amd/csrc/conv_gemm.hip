@@ -609,7 +609,8 @@ int mliis_conv2d_kernel_name(int Nimg, int H, int W, int Cred, int Nout, int ksi
     snprintf(buf, buf_len, "conv1x1_stream_k<%d, %d, %d>", r.sp.kc, r.sp.nt, precision);
   else if (r.route == ROUTE_KSPLIT)
     snprintf(buf, buf_len, "conv1x1_ksplit_k<%d, %d, 8, %d>", r.sp.kc, r.sp.nt, precision);
-  else if (g.sk_parts > 0 && !has_scale)   // (+ sk_fixup_k<NT> for the remainder tiles)
+  else if (g.sk_parts > 0 && !has_scale && !(precision == MLIIS_PREC_FP8 && ksize == 1))   // (+ sk_fixup_k<NT> for the remainder tiles;
+    // launch_gemm: an fp8 1x1 call has no stream-K form and runs its plan's tiles whole in conv_gemm_nk_k<..., 2>)
     snprintf(buf, buf_len, "conv_gemm_sk_k<%d, 2, false, %d>", g.nt, precision == MLIIS_PREC_FP8 ? MLIIS_PREC_BF16 : precision);
   else
     snprintf(buf, buf_len, "conv_gemm_nk_k<%d, %d, %d, %s, %s, %s, %d>", g.tm, g.nt, g.tm == 1 ? 2 : 1, has_scale ? "true" : "false",

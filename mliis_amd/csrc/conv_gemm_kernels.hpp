@@ -1606,12 +1606,13 @@ static void launch_gemm_t(const GemmPlan& g, const ConvGemmParams& p, hipStream_
 // The instances of the two 1x1 kernel families, one list each: the launch switches, the routing (route_conv: a planned <KC, NT> without
 // an instance takes the GEMM) and mliis_conv1x1_occupancy are all derived from these.
 // conv1x1_stream_k: X(KC, NT, AIN): KC 16-wide K groups (K <= 112), NT column tiles per wave, KC * NT <= 8; AIN = 0: no
-// conv1x1_stream_k<..., AIN = true> form (the planner never gives more than four column tiles)
+// conv1x1_stream_k<..., AIN = true> form.  stream_plan caps NT at two column tiles, so no shape reaches the eight NT >= 3 instances
+// any more (tests/conv_instances.py: UNREACHABLE keeps the list); every instance rounds both operands as the call's precision says.
 #define MLIIS_STREAM_INSTANCES(X)                                                                                            \
   X(1, 1, 1) X(1, 2, 1) X(1, 3, 1) X(1, 4, 1) X(1, 5, 0) X(1, 6, 0) X(1, 7, 0) X(1, 8, 0) X(2, 1, 1) X(2, 2, 1) X(2, 3, 1) \
   X(2, 4, 1) X(3, 1, 1) X(3, 2, 1) X(4, 1, 1) X(4, 2, 1) X(5, 1, 1) X(6, 1, 1) X(7, 1, 1)
 // conv1x1_ksplit_k: X(KC, NT): KC 16-wide K groups per wave (8 waves: K <= 128 KC), NT column tiles, KC * NT <= 8, NT <= 7; and the
-// three instances with KC * NT = 12 that the planner takes on the small maps (one workgroup per CU there: 256 registers)
+// three instances beyond that -- <4, 3>, <5, 2>, <6, 2> -- that the planner takes on the small maps (one workgroup per CU there: 256 registers)
 #define MLIIS_KSPLIT_INSTANCES(X)                                                                                  \
   X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 5) X(1, 6) X(1, 7) X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(3, 1) X(3, 2) X(4, 1) \
   X(4, 2) X(4, 3) X(5, 1) X(5, 2) X(6, 1) X(6, 2) X(7, 1)
