@@ -3,7 +3,8 @@ oracle ops on the same seeded inputs: the depthwise conv with the batch norm + s
 staged (efficientnet_model.py:185-196,266-271; utils.py:87-134), its one-pass backward (input gradient, filter gradient, stage 1 of
 the batch norm's backward), the plain forms without a batch norm, and the geometry corner cases of the march (one-step chunks, odd
 step counts, narrow last bands, channel tails, maps smaller than a band).  Tolerances as in test_ops_gpu.py: forward rel 2e-5,
-backward rel 1e-4 of the tensor's max-abs (fp32 kernels vs fp64 oracle)."""
+backward rel 1e-4 of the tensor's max-abs (fp32 kernels vs fp64 oracle).  The shapes of test_dwmarch_shapes march at most two steps per
+chunk (the pipeline's prologue alone); the long marches, per kernel instance, live in test_dwmarch_instances_gpu.py."""
 import pytest
 import torch
 
