@@ -308,8 +308,11 @@ int mliis_conv2d_bwd_data_gate(const float* dy, int lddy, const float* w, float*
  *      mliis_x3_image_blocks(...) workgroups of the pack launch (`first block` = running sum, total_blocks = their sum).
  *      mliis_conv2d_fwd_x3 / mliis_conv2d_bwd_data_x3: arguments as mliis_conv2d_fwd / mliis_conv2d_bwd_data with the image in place of
  *      wt / w (the channel window is the image's); activations are read straight from memory in matrix-core operand layout and split
- *      in registers; 256-row tiles, one 512-thread workgroup per CU, stream-K remainder with a deterministic fix-up launch (slabs in ws:
- *      mliis_conv2d_x3_workspace_floats); *stats_nblk = four blocks per 256-row tile.  Cred >= 32.
+ *      in registers; 256-row tiles, one 512-thread workgroup per CU, every tile's K chunks dealt stream-K fashion over the workgroups
+ *      with a deterministic fix-up launch (slabs in ws: mliis_conv2d_x3_workspace_floats); *stats_nblk = four blocks per 256-row tile.
+ *      Cred >= 32.  mliis_conv2d_x3_plan: plan[0..7] (eight ints) = {16-column tiles per workgroup tile NT, row tiles, column tiles,
+ *      0 (no tile is finished outside the parts), stream-K parts, K chunks per part, slab slots per tile, K chunks of 32 per tile};
+ *      the workspace holds row tiles x column tiles x slots x 256 x 16 NT floats.
  *      Stream contract (see "Streams" at the top): the workgroup claims its CU's whole register file, nothing of another stream is ever
  *      co-resident with these kernels -- they may run beside any other stream's work.  `image` must be the image packed for exactly this
  *      (Cred window, Nout, ksize, direction); image_bytes = its size, checked against mliis_x3_image_bytes(Cred, Nout, ksize). */

@@ -408,7 +408,9 @@ __global__ __launch_bounds__(1024) void x3_fixup_k(ConvGemmParams p, SkPlan k) {
 // receives its channel's four pixels: two reads make the eight k values of a 16x16x32 operand).  Workgroup = 8 waves = 4 blocks of 32
 // input channels x 2 halves of the column tiles (the two waves of a SIMD hold one half each: 12 + 9 fragment reads for 48 + 36 matrix
 // instructions per chunk and SIMD pair); tile, slabs and descriptor table are those of conv_filter_grad2_batched_k<2, NT> (one tap per
-// workgroup, the multitap form of the concat's sliver included), so the plan, the workspace and the batched fold do not change.
+// workgroup, the multitap form included), so the plan, the workspace and the batched fold do not change.  (The launch switch has
+// NT = 4..8: the 8-channel sliver of the decoder's concat plans two column tiles at 8 x 56 x 56 -- one block along x, 98 slabs -- and
+// stays on the fp32 instruction; the multitap branch runs here once column blocks x slabs fill the chip: 8281 pixels x 920 columns, 66049 x 68.)
 typedef short x3_v4s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 ds_read_tr16(const char* p) {
   const x3_v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_v4s __attribute__((address_space(3)))*)(p));
@@ -820,11 +822,13 @@ size_t mliis_conv2d_x3_workspace_floats(int Nimg, int H, int W, int Cred, int No
   return x3_plan((long long)Nimg * H * W, Nout, ksize * ksize, Cred, x3_num_cus()).slab_floats();
 }
 
-// tiling of an x3 call: plan[0..5] = {column tiles NT, row tiles, column tiles per row, whole-tile workgroups, stream-K parts, K chunks per part}
+// tiling of an x3 call: plan[0..7] = {16-column tiles per workgroup tile NT (the instance: conv_x3_k<NT>, x3_fixup_k<NT>), row tiles of 256,
+// column tiles of 16 NT, tiles finished outside the stream-K parts (always 0: every tile goes through the parts), stream-K parts (= workgroups
+// of conv_x3_k), K chunks per part, slab slots per tile, K chunks of 32 per tile}
 int mliis_conv2d_x3_plan(int Nimg, int H, int W, int Cred, int Nout, int ksize, int* plan) {
   MLIIS_REQUIRE(plan, MLIIS_ERR_ARG, "conv2d_x3_plan: null pointer");
   const X3Plan g = x3_plan((long long)Nimg * H * W, Nout, ksize * ksize, Cred, x3_num_cus());
-  plan[0] = g.nt; plan[1] = g.gx; plan[2] = g.gy; plan[3] = g.full; plan[4] = g.parts; plan[5] = g.ipp;
+  plan[0] = g.nt; plan[1] = g.gx; plan[2] = g.gy; plan[3] = g.full; plan[4] = g.parts; plan[5] = g.ipp; plan[6] = g.smax; plan[7] = g.nchunks;
   return MLIIS_OK;
 }
 

@@ -605,7 +605,9 @@ def x3_image_of(w, mode, ci_begin=0, cin=None):
 
 
 def conv2d_x3_kernel_name(N, H, W, cred, nout, k):
-    """The instantiation an x3 call launches, as rocprofv3 prints it (+ x3_fixup_k<NT> for the stream-K tiles)."""
+    """The instantiation an x3 call launches, as rocprofv3 prints it (+ x3_fixup_k<NT>: every tile goes through the stream-K parts and
+    is finished by the fix-up).  plan[0..7] of mliis_conv2d_x3_plan: NT, row tiles, column tiles, 0, parts, chunks per part, slab slots per
+    tile, chunks per tile."""
     plan = (C.c_int * 8)()
     lib.call("mliis_conv2d_x3_plan", N, H, W, cred, nout, k, plan)
     return "conv_x3_k<%d>" % plan[0]
@@ -810,7 +812,8 @@ class FilterBatch:
                 self.tables.append((torch.tensor(rows, dtype=torch.int64, device=self.device), len(rows), first, tmf, nt, int(sc), wide))
 
     def launch(self, precision="fp32"):
-        """precision "fp32x3": the groups of 128-channel tiles as fp32-equivalent split products on the bf16 matrix cores
+        """precision "fp32x3": the groups of 128-channel tiles with 4..8 column tiles and no x_scale (plan TMF = 2: 128 input channels, or
+        a last 128-channel tile more than half full; the multitap form too) as fp32-equivalent split products on the bf16 matrix cores
         (MLIIS_PREC_F32X3), the other groups on the fp32 instruction."""
         if self.tables is None:
             self._build()

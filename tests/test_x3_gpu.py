@@ -209,7 +209,9 @@ def test_x3_filter_gradients_match_the_oracle(N, H, Cbuf, Cin, Cout, k, dil, x3)
 
 def test_x3_filter_gradient_of_the_concat_sliver_takes_the_multitap_form():
     """The 8-channel tail of the 136-channel concat under a 3x3 conv: all nine taps in ONE 128-row block (72 flattened (tap, channel)
-    rows), in the same launch as a plain problem of the group."""
+    rows).  (At this size the plan is TMF 2, NT 2, multitap: launch_filter_batched_x3 has no case for two column tiles, so "fp32x3"
+    runs the multitap path of the NATIVE fp32 instruction here; the multitap body of conv_filter_x3_batched_k is launched by
+    tests/test_x3_instances_gpu.py on maps of 8281 pixels and more.)"""
     from mliis_amd import ops
     d = dev()
     N, H, Cbuf, Cout = 8, 56, 136, 112
