@@ -33,7 +33,7 @@ from ._lib import MliisError, lib, score_lib, steplog_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
-from .plan import _Plan
+from .plan import _Plan, layer_names
 from .steplog import decode as decode_step_log
 
 
@@ -168,7 +168,8 @@ class Learner(_Passes):
         self.drop_keep_dev = torch.tensor([1.0 - self.final_layer_dropout_rate], dtype=torch.float32, device=self.device)
         self._drop_keep_val = 1.0 - self.final_layer_dropout_rate
         self._rng_now = None   # (generator state, mask plan) of a training step that draws its masks: set by _train_sequence, taken by _forward
-        self._pname()
+        # variable names per layer (plan.layer_names): passes.py, the tools and the tests read them here
+        self.n_stem, self.n_blocks, self.n_rsd, self.n_rsd_up, self.n_skipdec, self.n_final, self.n_aspp = layer_names(self.arch)
         # fp32x3: weight images of the decoder's 3x3 convs (the dilated branch over the whole concat, the fuse conv over its convolved
         # channels), both directions, re-split once per step beside the shadow transpose
         self.x3 = None
@@ -185,37 +186,6 @@ class Learner(_Passes):
                         self.x3.add(name, "bwd", A.t_off[name], kk, cin_total, cout, 0, win)
             self.x3.finish()
         torch.cuda.synchronize(self.device)   # arena was initialised on the default stream; steps run on self.stream
-
-    # ------------------------------------------------------------------------------------------- names
-    def _pname(self):
-        fe = self.arch.name
-        self.n_stem = (f"{fe}/stem/conv2d/kernel", f"{fe}/stem/tpu_batch_normalization")
-        self.n_blocks = []
-        for b in self.arch.executed():
-            s = f"{fe}/blocks_{b.idx}"
-            bns = [f"{s}/tpu_batch_normalization", f"{s}/tpu_batch_normalization_1", f"{s}/tpu_batch_normalization_2"]
-            cvs = [f"{s}/conv2d/kernel", f"{s}/conv2d_1/kernel"]
-            d = {}
-            if b.expand != 1:
-                d["w_exp"], d["bn0"] = cvs.pop(0), bns.pop(0)
-            d["w_dw"], d["bn1"] = f"{s}/depthwise_conv2d/depthwise_kernel", bns.pop(0)
-            d["se"] = (f"{s}/se/conv2d/kernel", f"{s}/se/conv2d/bias", f"{s}/se/conv2d_1/kernel", f"{s}/se/conv2d_1/bias")
-            d["w_proj"], d["bn2"] = cvs.pop(0), bns.pop(0)
-            self.n_blocks.append(d)
-        self.n_rsd, self.n_rsd_up = [], []
-        for m in self.arch.rsd:
-            s = f"decode/decode_skip_connections_{m.scope_index}"
-            sfx = ["", "_1", "_2", "_3"]
-            trip = lambda x: (f"{s}/conv2d{x}/kernel", f"{s}/conv2d{x}/bias", f"{s}/batch_normalization{x}")   # noqa: E731
-            self.n_rsd_up.append(trip(sfx.pop(0)) if m.upsample_conv else None)   # (created first in the scope, efficientlab.py:213-215)
-            self.n_rsd.append([trip(sfx.pop(0)) for _ in range(3)])
-        s = "decode/decode_skip_connections"   # --skip_decoding: (1x1 kernel, its BN), then per sep_conv (dw kernel, BN, 1x1 kernel, BN)
-        self.n_skipdec = ((f"{s}/conv2d/kernel", f"{s}/batch_normalization"),
-                          [(f"{s}/depthwise_conv2d{'' if j == 0 else '_%d' % j}/depthwise_kernel", f"{s}/batch_normalization_{2 * j + 1}",
-                            f"{s}/conv2d_{j + 1}/kernel", f"{s}/batch_normalization_{2 * j + 2}") for j in range(2)])
-        self.n_final = ("decode/final_layer_weights/kernel", "decode/final_layer_weights/bias")
-        s = "decode/spatial_pyramid_pooling"
-        self.n_aspp = [(f"{sc}/conv2d/kernel", f"{sc}/conv2d/bias") for sc in (f"{s}/branch_0", f"{s}/branch_1", f"{s}/branch_2", s)]
 
     # ------------------------------------------------------------------------------------------- variable state
     @property

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import torch
@@ -240,6 +241,10 @@ def stem_conv_fwd_stats_floats(N, H, W, Co):
     return lib.size("mliis_stem_conv_fwd_stats_floats", N, H, W, Co)
 
 
+def stem_conv_bwd_filter_floats(N, H, W, Co):
+    return lib.size("mliis_stem_conv_bwd_filter_workspace_floats", N, H, W, Co)
+
+
 def stem_conv_bwd_filter(x, dz, idx=None, out=None, ws: Optional[Workspace] = None, partial=None):
     S, H, W, _ = x.shape
     N, _, _, Co = dz.shape
@@ -250,8 +255,7 @@ def stem_conv_bwd_filter(x, dz, idx=None, out=None, ws: Optional[Workspace] = No
                  _stream())
         return None
     ws = ws or default_ws()
-    need = lib.size("mliis_stem_conv_bwd_filter_workspace_floats", N, H, W, Co)
-    buf = ws.get(need)
+    buf = ws.get(stem_conv_bwd_filter_floats(N, H, W, Co))
     out = torch.empty((3, 3, 3, Co), dtype=torch.float32, device=x.device) if out is None else out
     lib.call("mliis_stem_conv_bwd_filter", _ptr(x), _ptr(idx), _ptr(dz), _ptr(out), N, H, W, Co, _MEAN3, _STD3, _ptr(buf), buf.numel(),
              _stream())
@@ -299,6 +303,10 @@ def dwconv_bwd_data(dy, w, stride, in_hw, out=None, bn=None, part=None):
     return out
 
 
+def dwconv_bwd_filter_floats(N, H, W, C_, k, stride):
+    return lib.size("mliis_dwconv_bwd_filter_workspace_floats", N, H, W, C_, k, stride)
+
+
 def dwconv_bwd_filter(x, dy, k, stride, out=None, ws: Optional[Workspace] = None, partial=None):
     N, H, W, C_ = x.shape
     _dense(x, dy, partial)
@@ -307,7 +315,7 @@ def dwconv_bwd_filter(x, dy, k, stride, out=None, ws: Optional[Workspace] = None
         lib.call("mliis_dwconv_bwd_filter", _ptr(x), _ptr(dy), None, N, H, W, C_, k, stride, _ptr(partial), partial.numel(), _stream())
         return None
     ws = ws or default_ws()
-    buf = ws.get(lib.size("mliis_dwconv_bwd_filter_workspace_floats", N, H, W, C_, k, stride))
+    buf = ws.get(dwconv_bwd_filter_floats(N, H, W, C_, k, stride))
     out = torch.empty((k, k, C_, 1), dtype=torch.float32, device=x.device) if out is None else out
     meta = dict(bytes=4.0 * (x.numel() + k * k * C_), shape=(N, H, W, C_, k, stride)) if PROFILE is not None else {}   # filter: X + dW
     _timed("dwconv_bwd_filter", meta, lambda: lib.call("mliis_dwconv_bwd_filter", _ptr(x), _ptr(dy), _ptr(out), N, H, W, C_, k, stride, _ptr(buf),
@@ -338,6 +346,15 @@ def dwconv_bn_fwd(z, w, stride, bn=None, part=None, nblk=0, out=None, stats_part
     if stats_part is not None:
         return out, nb.value
     return out
+
+
+def dwconv_bn_supported(N, H, W, C_, k, stride) -> bool:
+    """True when the row-marching entry points (dwconv_bn_fwd / _bwd, mbconv_dw_bwd_march) take this layer."""
+    return bool(lib.raw("mliis_dwconv_bn_supported")(N, H, W, C_, k, stride))
+
+
+def dwconv_bn_fwd_blocks(N, H, W, C_, k, stride) -> int:
+    return int(lib.raw("mliis_dwconv_bn_fwd_blocks")(N, H, W, C_, k, stride))
 
 
 def dwconv_bn_bwd_blocks(N, H, W, C_, k, stride) -> int:
@@ -698,6 +715,10 @@ def conv2d_bwd_data(dy, w, dil=1, ci_begin=0, ci_count=None, out=None, accumulat
     return out
 
 
+def conv2d_bwd_filter_floats(N, H, W, Cin, Cout, k):
+    return lib.size("mliis_conv2d_bwd_filter_workspace_floats", N, H, W, Cin, Cout, k)
+
+
 def conv2d_bwd_filter(x, dy, k, dil=1, out=None, accumulate=False, ws: Optional[Workspace] = None, x_scale=None, ci_begin=0, partial=None,
                       precision="fp32"):
     """Writes rows [ci_begin, ci_begin + x.channels) of `out` ([k,k,Cin_total,Cout]; Cin_total = x.channels when out is None).
@@ -720,12 +741,35 @@ def conv2d_bwd_filter(x, dy, k, dil=1, out=None, accumulate=False, ws: Optional[
     out = torch.empty((k, k, Cin, Cout), dtype=torch.float32, device=x.device) if out is None else out
     Cin_total = out.shape[2]
     ws = ws or default_ws()
-    buf = ws.get(lib.size("mliis_conv2d_bwd_filter_workspace_floats", N, H, W, Cin, Cout, k))
+    buf = ws.get(conv2d_bwd_filter_floats(N, H, W, Cin, Cout, k))
     meta = dict(flops=2.0 * N * H * W * k * k * Cin * Cout, shape=(N, H, W, Cin, Cout, k, dil)) if PROFILE is not None else {}
     _timed("conv2d_bwd_filter", meta, lambda: lib.call("mliis_conv2d_bwd_filter", _ptr(x), ldx, _ptr(x_scale), _ptr(dy), lddy, _ptr(out), N, H, W, Cin_total, ci_begin,
                                                        Cin, Cout, k,
                                                        dil, int(accumulate), _ptr(buf), buf.numel(), prec, _stream()))
     return out
+
+
+class FilterProblem(namedtuple("FilterProblem", "x dy x_scale slabs ldx lddy N H W Cin Cout k x_bf16 dy_bf16 dil rows_per_split multitap gx gy gz")):
+    """One deferred filter gradient: the four addresses (x_scale 0: none), the shape, x_bf16 / dy_bf16 (X / dY stored as bf16: an expanded
+    MBConv tensor under `--precision bf16-storage`) and the tiling: mliis_conv2d_bwd_filter_plan's, or FilterBatch's re-tiling of it."""
+
+    @property
+    def blocks(self):
+        return self.gx * self.gy * self.gz
+
+    def words(self, first):
+        """The problem's row of a mliis_conv2d_bwd_filter_batched table, its workgroups starting at block `first` of the grid: the 16
+        words conv_filter_grad2_batched_k decodes (the comment above kFilterDescWords in csrc/conv_gemm_kernels.hpp states the layout;
+        this is its only writer)."""
+        return [self.x, self.dy, self.x_scale, self.slabs, self.ldx, self.lddy, self.N, self.H, self.W, self.Cin, self.Cout,
+                self.k | (self.x_bf16 << 8) | (self.dy_bf16 << 9), self.dil, self.rows_per_split | (self.multitap << 32),
+                self.gx | (self.gy << 20) | (self.gz << 40), first]
+
+
+# one launch of FilterBatch: device int64 [nprob][16], its grid and kernel instantiation; wide: None, or WideTable(table, blocks) of the
+# same problems tiled for the 256-channel fp32x3 form
+FilterTable = namedtuple("FilterTable", "table nprob blocks tmf nt has_scale wide")
+WideTable = namedtuple("WideTable", "table blocks")
 
 
 class FilterBatch:
@@ -735,8 +779,9 @@ class FilterBatch:
 
     def __init__(self, device):
         self.device = device
-        self.groups = {}          # (tmf, nt, has_scale) -> list of rows
-        self.tables = None
+        self.groups = {}          # (tmf, nt, has_scale) -> list of FilterProblem
+        self.tables = None        # list of FilterTable
+        self.flops = 0.0
         self._keep = []           # the tensors whose addresses the tables hold
 
     def add(self, x, dy, k, dil, partial, x_scale=None):
@@ -749,11 +794,10 @@ class FilterBatch:
         tmf, nt, multitap, gx, gy, gz, rps = [int(v) for v in plan[:7]]
         if partial.numel() < gz * k * k * Cin * Cout:
             raise MliisError("FilterBatch: slab region too small")
-        # (ksize word: bits 8 / 9 = X / dY stored as bf16 -- an expanded MBConv tensor under `--precision bf16-storage`)
-        row = [x.data_ptr(), dy.data_ptr(), x_scale.data_ptr() if x_scale is not None else 0, partial.data_ptr(), ldx, lddy, N, H, W, Cin,
-               Cout, k | (_dt(x) << 8) | (_dt(dy) << 9), dil, rps | (multitap << 32), gx | (gy << 20) | (gz << 40), 0]
-        self.groups.setdefault((tmf, nt, x_scale is not None), []).append((row, gx * gy * gz, bool(multitap)))
-        self.flops = getattr(self, "flops", 0.0) + 2.0 * N * H * W * k * k * Cin * Cout
+        self.groups.setdefault((tmf, nt, x_scale is not None), []).append(FilterProblem(
+            x.data_ptr(), dy.data_ptr(), x_scale.data_ptr() if x_scale is not None else 0, partial.data_ptr(), ldx, lddy, N, H, W, Cin, Cout,
+            k, _dt(x), _dt(dy), dil, rps, multitap, gx, gy, gz))
+        self.flops += 2.0 * N * H * W * k * k * Cin * Cout
         self._keep += [x, dy, partial, x_scale]
         self.tables = None
 
@@ -774,42 +818,36 @@ class FilterBatch:
         groups = {k: list(v) for k, v in self.groups.items()}
         for (tmf, nt, sc) in sorted(groups):
             items = groups[(tmf, nt, sc)]
-            if not (tmf == 1 and nt in (1, 2, 3, 6) and items and not any(mt for _, _, mt in items) and
-                    sum(b for _, b, _ in items) < self.MERGE_MAX_BLOCKS):
+            if not (tmf == 1 and nt in (1, 2, 3, 6) and items and not any(p.multitap for p in items) and
+                    sum(p.blocks for p in items) < self.MERGE_MAX_BLOCKS):
                 continue
-            moved = []
-            for row, _, mt in items:
-                cout = row[10]
-                gx, gz = row[14] & 0xfffff, row[14] >> 40
-                gy = -(-cout // 64)
-                moved.append((row[:14] + [gx | (gy << 20) | (gz << 40), 0], gx * gy * gz, mt))
-            groups.setdefault((1, 4, sc), []).extend(moved)
+            groups.setdefault((1, 4, sc), []).extend(p._replace(gy=-(-p.Cout // 64)) for p in items)
             del groups[(tmf, nt, sc)]
         return groups
+
+    def _table(self, problems):
+        """(device table, blocks) of problems laid one after the other in a grid."""
+        rows, first = [], 0
+        for p in problems:
+            rows.append(p.words(first))
+            first += p.blocks
+        return torch.tensor(rows, dtype=torch.int64, device=self.device), first
 
     def _build(self):
         self.tables = []
         for (tmf, nt, sc), items in sorted(self._merged_groups().items()):
             for i0 in range(0, len(items), 64):          # (the kernel scans at most 64 rows)
-                rows, first = [], 0
-                for row, blocks, _ in items[i0:i0 + 64]:
-                    rows.append(row[:15] + [first])
-                    first += blocks
+                probs = items[i0:i0 + 64]
+                table, blocks = self._table(probs)
                 # the same problems tiled for conv_filter_x3_batched_k's 256-channel form (MLIIS_PREC_F32X3, TMF passed as 4): a problem with
                 # more than 128 input channels takes gx = taps * ceil(Cin / 256) workgroups along x; slabs, pixel splits and fold unchanged
                 wide = None
                 if tmf == 2 and not sc and 4 <= nt <= 8 and self.X3_WIDE:
-                    wrows, wfirst = [], 0
-                    for row, _, _ in items[i0:i0 + 64]:
-                        cin, kk, multitap = row[9], row[11] & 0xff, (row[13] >> 32) & 1
-                        gx, gy, gz = row[14] & 0xfffff, (row[14] >> 20) & 0xfffff, row[14] >> 40
-                        if not multitap and cin > 128:
-                            gx = kk * kk * ((cin + 255) // 256)
-                        wrows.append(row[:14] + [gx | (gy << 20) | (gz << 40), wfirst])
-                        wfirst += gx * gy * gz
-                    if wfirst != first:   # (at least one problem is tiled differently)
-                        wide = (torch.tensor(wrows, dtype=torch.int64, device=self.device), wfirst)
-                self.tables.append((torch.tensor(rows, dtype=torch.int64, device=self.device), len(rows), first, tmf, nt, int(sc), wide))
+                    wide = WideTable(*self._table([p._replace(gx=p.k * p.k * -(-p.Cin // 256)) if not p.multitap and p.Cin > 128 else p
+                                                   for p in probs]))
+                    if wide.blocks == blocks:   # (no problem is tiled differently)
+                        wide = None
+                self.tables.append(FilterTable(table, len(probs), blocks, tmf, nt, int(sc), wide))
 
     def launch(self, precision="fp32"):
         """precision "fp32x3": the groups of 128-channel tiles with 4..8 column tiles and no x_scale (plan TMF = 2: 128 input channels, or
@@ -818,15 +856,15 @@ class FilterBatch:
         if self.tables is None:
             self._build()
         prec = 3 if precision == "fp32x3" else _prec(precision)
-        if prec in (0, 3) and any((row[11] >> 8) for items in self.groups.values() for row, _, _ in items):
+        if prec in (0, 3) and any(p.x_bf16 or p.dy_bf16 for items in self.groups.values() for p in items):
             raise MliisError("FilterBatch: bf16 tensors need the bf16-operand instances (precision 'bf16')")
         def issue():
-            for table, nprob, blocks, tmf, nt, sc, wide in self.tables:
-                if prec == 3 and wide is not None:
-                    lib.call("mliis_conv2d_bwd_filter_batched", _ptr(wide[0]), nprob, wide[1], 4, nt, sc, prec, _stream())
+            for t in self.tables:
+                if prec == 3 and t.wide is not None:
+                    lib.call("mliis_conv2d_bwd_filter_batched", _ptr(t.wide.table), t.nprob, t.wide.blocks, 4, t.nt, t.has_scale, prec, _stream())
                 else:
-                    lib.call("mliis_conv2d_bwd_filter_batched", _ptr(table), nprob, blocks, tmf, nt, sc, prec, _stream())
-        _timed("conv2d_bwd_filter_batched", dict(flops=getattr(self, "flops", 0.0)) if PROFILE is not None else {}, issue)
+                    lib.call("mliis_conv2d_bwd_filter_batched", _ptr(t.table), t.nprob, t.blocks, t.tmf, t.nt, t.has_scale, prec, _stream())
+        _timed("conv2d_bwd_filter_batched", dict(flops=self.flops) if PROFILE is not None else {}, issue)
 
     def __len__(self):
         return sum(len(v) for v in self.groups.values())
@@ -1382,6 +1420,11 @@ def darc1(logits, weight, dlogits=None, out=None, ws: Optional[Workspace] = None
     ws = ws or default_ws()
     buf = ws.get(2048)
     lib.call("mliis_darc1", _ptr(_chk(logits)), N, logits.numel() // N, float(weight), _ptr(dlogits), _ptr(out), _ptr(buf), buf.numel(), _stream())
+
+
+def fold_tile_outputs() -> int:
+    """Consecutive outputs of a descriptor that one workgroup (tile) of fold_batched reduces."""
+    return int(lib.raw("mliis_fold_tile_outputs")())
 
 
 def fold_batched(part_base, out_base, desc, total_tiles, se_desc=None, se_tiles=0):
