@@ -148,6 +148,17 @@ _EXT = [
                                   "off = nothing (logged with --inner-loop-log), skip = the meta-iteration's update is left out on all "
                                   "ranks, abort = stop with an error before the update and before any checkpoint is written; skip and "
                                   "abort imply --inner-loop-log")),
+    ("--inner-loop-layer-log", dict(action="store_true",
+                                    help="log the inner loop per tensor as well: every training step also writes, for each trainable tensor, "
+                                         "the norm and largest magnitude of its gradient and of its parameters and their non-finite counts to "
+                                         "a second ring on the device (csrc/layerlog.hip: two more launches in the step's graph), and every "
+                                         "task the per-tensor distance it moved from the initialisation; every "
+                                         "--inner-loop-layer-log-interval meta-iterations one line goes to "
+                                         "<checkpoint>/train/inner_loop_layers.jsonl, and a non-finite step is attributed to tensors.  "
+                                         "Implies --inner-loop-log")),
+    ("--inner-loop-layer-log-interval", dict(type=int, default=100, metavar="N",
+                                             help="with --inner-loop-layer-log: read the per-tensor rings and write a line every N "
+                                                  "meta-iterations (the checkpoint cadence)")),
 ]
 
 
@@ -187,8 +198,13 @@ def stored_image_size(a) -> int:
 
 
 def inner_loop_log(a) -> bool:
-    """--inner-loop-log, or an --on-divergence that needs it."""
-    return bool(getattr(a, "inner_loop_log", False)) or getattr(a, "on_divergence", "off") != "off"
+    """--inner-loop-log, or an --on-divergence / --inner-loop-layer-log that needs it."""
+    return bool(getattr(a, "inner_loop_log", False)) or getattr(a, "on_divergence", "off") != "off" or inner_loop_layer_log(a)
+
+
+def inner_loop_layer_log(a) -> bool:
+    """--inner-loop-layer-log."""
+    return bool(getattr(a, "inner_loop_layer_log", False))
 
 
 def model_kwargs(a) -> dict:
@@ -201,6 +217,8 @@ def model_kwargs(a) -> dict:
     if getattr(a, "meta_fine_tune_steps_on_train_val", 0) > 0:   # (that phase adapts with the searched step count, two steps per batch)
         steps = max(steps, 2 * a.max_steps)
     log = dict(step_log=capacity_for(steps)) if inner_loop_log(a) else {}
+    if inner_loop_layer_log(a):   # (the per-tensor ring is sized like the step log's: the same rows)
+        log["layer_log"] = True
     return dict(feature_extractor_name=a.feature_extractor_name, image_size=a.image_size, rsd=a.rsd or None,
                 learning_rate=a.learning_rate, optimizer="sgd" if a.sgd else "adam", l2=a.l2, l1=a.l1, darc1=a.darc1,
                 dice=("dice" in a.loss_name), label_smoothing=a.label_smoothing, final_layer_dropout_rate=a.final_layer_dropout_rate,
@@ -229,7 +247,9 @@ def train_kwargs(a) -> dict:
                 meta_batch_size=a.meta_batch, meta_iters=a.meta_iters, eval_inner_batch_size=a.eval_batch, eval_inner_iters=a.eval_iters,
                 eval_interval=a.eval_interval, weight_decay_rate=a.weight_decay, transductive=a.transductive, meta_fn=_meta_fn(a),
                 aug_rate=a.aug_rate, device_metrics=bool(getattr(a, "device_metrics", False)),
-                **(dict(inner_loop_log=True, on_divergence=a.on_divergence) if inner_loop_log(a) else {}))
+                **(dict(inner_loop_log=True, on_divergence=a.on_divergence) if inner_loop_log(a) else {}),
+                **(dict(inner_loop_layer_log=True, inner_loop_layer_log_interval=a.inner_loop_layer_log_interval)
+                   if inner_loop_layer_log(a) else {}))
 
 
 def evaluate_kwargs(a) -> dict:

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import ops, spec
-from ._lib import MliisError, lib, score_lib, steplog_lib
+from . import layerlog
+from ._lib import MliisError, layerlog_lib, lib, score_lib, steplog_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
@@ -44,7 +45,7 @@ class Learner(_Passes):
                  spatial_pyramid_pooling: bool = False, skip_decoding: bool = False, drop_connect: bool = True, seed: int = 0,
                  device="cuda:0", use_graph: bool = True, max_shots: int = 16, matmul_precision: str = "fp32",
                  small_fused: Optional[bool] = None, dw_march: Optional[bool] = None, fuse_bn2: Optional[bool] = None, fuse_head: Optional[bool] = None,
-                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0):
+                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam' (Adam with beta1=0, the reference default)")
         if not torch.cuda.is_available():
@@ -148,6 +149,29 @@ class Learner(_Passes):
             self._log_cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._log_ws = ops.steplog_workspace(self.device)
             self._log_pin = torch.zeros(self.step_log * words + 1, dtype=torch.int32).pin_memory()
+        # layer_log = True (needs step_log = CAPACITY > 0): two more launches in front of the step log's (ops.layerlog_append, captured with
+        # it) write one record PER TRAINABLE TENSOR -- norm and largest magnitude of its gradient and of its parameters, their non-finite
+        # counts and where the first one sits -- into row (step log cursor) % CAPACITY of a [CAPACITY, T] ring: row k is the step of the
+        # step log's record k; read_layer_log() fetches them.  A second ring of the same size takes layer_delta()'s rows (||a - b|| per
+        # tensor).  False (the default): nothing is allocated and the step issues the launches it issues without the argument.
+        self.layer_log = bool(layer_log)
+        if self.layer_log and not self.step_log:
+            raise ValueError("layer_log=True needs a step log (step_log=CAPACITY > 0): its rows are addressed by the step log's cursor")
+        self._layer_table = self._layer_ring = self._layer_ws = self._layer_pin = self._delta_ring = self._delta_ws = None
+        self._log_window = (0, 0)   # the counter values the last read_step_log() read between
+        if self.layer_log:
+            layerlog_lib.load()  # (a missing library is an error here, not at the first step)
+            A = self.arena
+            self._layer_table = ops.layerlog_table([p.size for p in A.trainable], self.device)
+            if self._layer_table.n != A.n_trainable_padded or \
+                    any(int(q) * 4 != A.t_off[p.name] for q, p in zip(self._layer_table.segs[:, 0].tolist(), A.trainable)):
+                raise MliisError("the per-tensor log's table does not follow the arena's layout")
+            T, words = len(A.trainable), layerlog_lib.size("mliis_layerlog_record_words")
+            self._layer_ring = torch.zeros((self.step_log, T, words), dtype=torch.int32, device=self.device)
+            self._delta_ring = torch.zeros((self.step_log, T, words), dtype=torch.int32, device=self.device)
+            self._layer_ws = ops.layerlog_workspace(self._layer_table)
+            self._delta_ws = ops.layerlog_workspace(self._layer_table)
+            self._layer_pin = torch.zeros(self.step_log * T * words + 1, dtype=torch.int32).pin_memory()
         self.plans: Dict[object, _Plan] = {}   # key: batch size (training plan) or (batch size, "infer") in bf16-storage mode
         self.max_shots = max_shots
         H = image_size
@@ -533,6 +557,8 @@ class Learner(_Passes):
                 ops.darc1(logits, spec.L2_WEIGHT, dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
         self._backward(P, self.shots_x, P.idx, head_fused=head_fused)
         self._apply()
+        if self.layer_log:   # the same two arenas per tensor, into the row the step log's cursor names (read here, advanced below)
+            ops.layerlog_append(self.arena.grad, self.arena.theta, self._layer_table, self._layer_ws, self._log_cursor, out=self._layer_ring)
         if self.step_log:   # the step's record: P.loss_out is final here, arena.grad is what _apply() consumed, theta what it left
             ops.steplog_append(P.loss_out, self.lr_dev, self.arena.grad, self.arena.theta, self._log_ws, self._log_cursor, out=self._log_ring)
 
@@ -625,6 +651,7 @@ class Learner(_Passes):
         host = self._log_pin.numpy()
         cursor = int(host[n]) & 0xFFFFFFFF
         records, dropped = decode_step_log(host[:n].reshape(self.step_log, -1), cursor, self._log_seen)
+        self._log_window = (self._log_seen, cursor)
         self._log_seen = cursor
         return records, dropped
 
@@ -636,6 +663,62 @@ class Learner(_Passes):
         """Forget the records of the steps issued so far without reading them (no synchronisation): the next read_step_log() starts behind
         them."""
         self._log_seen = self._log_issued & 0xFFFFFFFF
+
+    # ------------------------------------------------------------------------------------------- per-tensor log
+    @property
+    def layer_log_names(self) -> List[str]:
+        """The tensor names of a layer-log row, in table order (arena.trainable)."""
+        return [p.name for p in self.arena.trainable]
+
+    def _fetch_layer_ring(self, ring):
+        """(host words [rows, T, 8], device cursor) after the learner's stream has drained; ring and cursor through pinned memory."""
+        n = ring.numel()
+        with torch.cuda.stream(self.stream):
+            self._layer_pin[:n].copy_(ring.view(-1), non_blocking=True)
+            self._layer_pin[n:].copy_(self._log_cursor, non_blocking=True)
+        self.stream.synchronize()
+        host = self._layer_pin.numpy()
+        return host[:n].reshape(tuple(ring.shape)), int(host[n]) & 0xFFFFFFFF
+
+    def read_layer_log(self, last_read: bool = False):
+        """(records [steps, T], dropped): the per-tensor rows (layerlog.RECORD_DTYPE: x = gradient, y = parameters; T tensors in
+        layer_log_names order) of the steps read_step_log() would return now, and how many of those steps' rows the ring no longer held.
+        Nothing is consumed: the "seen" cursor is the step log's and only read_step_log() / skip_step_log() advance it, so the rows stay
+        readable until then -- and after it as well: last_read=True returns the rows of exactly the steps the LAST read_step_log()
+        returned (as far as the ring still holds them: steps issued since then overwrite the oldest).  Waits for the learner's stream."""
+        if not self.layer_log:
+            raise MliisError("this Learner was built without a per-tensor log (layer_log=False)")
+        host, cursor = self._fetch_layer_ring(self._layer_ring)
+        if not last_read:
+            return layerlog.decode(host, cursor, self._log_seen)
+        first, end = self._log_window
+        records, dropped = layerlog.decode(host, end, first)
+        lost = min(len(records), max(0, ((cursor - first) & 0xFFFFFFFF) - self.step_log - dropped))   # overwritten since that read
+        return records[lost:], dropped + lost
+
+    def layer_delta(self, a: torch.Tensor, b: torch.Tensor, row: int):
+        """Launch, on the learner's stream, the per-tensor reduction of a - b (and of b) into row `row` of the delta ring: a, b arena-shaped
+        fp32 device buffers (export_trainable()'s layout).  read_layer_deltas() fetches rows."""
+        if not self.layer_log:
+            raise MliisError("this Learner was built without a per-tensor log (layer_log=False)")
+        if not 0 <= int(row) < self.step_log:
+            raise ValueError("layer_delta row {} outside the ring of {} rows".format(row, self.step_log))
+        self._in()
+        with torch.cuda.stream(self.stream):
+            for t in (a, b):
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(self.stream)
+            ops.layerlog_append(a, b, self._layer_table, self._delta_ws, None, out=self._delta_ring, row_offset=int(row), mode="delta")
+
+    def read_layer_deltas(self, rows: Sequence[int]) -> np.ndarray:
+        """records [len(rows), T] of the delta ring (layerlog.RECORD_DTYPE: x = a - b, y = b).  Waits for the learner's stream."""
+        if not self.layer_log:
+            raise MliisError("this Learner was built without a per-tensor log (layer_log=False)")
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.step_log for r in rows):
+            raise ValueError("layer delta rows {} outside the ring of {} rows".format(rows, self.step_log))
+        host, _ = self._fetch_layer_ring(self._delta_ring)
+        return host.view(np.uint32)[rows].copy().view(layerlog.RECORD_DTYPE).reshape(len(rows), host.shape[1])
 
     def _fill_masks(self, P: _Plan, dc_scales, dropout_mask, drop_rate=None, aspp_masks=None) -> bool:
         """Masks handed in by the caller (parity tests) are copied into the plan's buffers; returns True when the step has to draw its

@@ -11,9 +11,11 @@ import os
 from collections import namedtuple
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
-from ._lib import MliisError, data_lib, lib, score_lib, steplog_lib
+from . import layerlog as _layerlog
+from ._lib import MliisError, data_lib, layerlog_lib, lib, score_lib, steplog_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1409,6 +1411,93 @@ def steplog_append(loss4, lr_dev, grad, theta, ws, cursor, out=None, capacity=No
     _timed("steplog_append", {}, lambda: steplog_lib.call("mliis_steplog_append", _ptr(loss4), _ptr(lr_dev), _ptr(grad), _ptr(theta),
                                                           grad.numel(), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()),
                                                           int(out.shape[0]), C.c_void_p(cursor.data_ptr()), _stream()))
+    return out
+
+
+class LayerTable:
+    """The device tables of one per-tensor log (layerlog_table): chunks int32 [nchunks, 4], segs int32 [T, 4], validated on the host before
+    they were uploaded; n: the floats of the arenas they address."""
+
+    def __init__(self, chunks: torch.Tensor, segs: torch.Tensor, n: int):
+        self.chunks, self.segs, self.n = chunks, segs, int(n)
+        self.nchunks, self.T = int(chunks.shape[0]), int(segs.shape[0])
+
+
+def layerlog_table(sizes, device, chunks=None, segs=None, n=None) -> LayerTable:
+    """The tables of layerlog_append for arenas that pack tensors of `sizes` elements, each padded to 4 floats (layerlog.chunk_table with
+    the library's chunk size), on `device`.  chunks / segs / n: tables built elsewhere instead (sizes is then ignored).  Either way they
+    are validated here, once, on the host (layerlog.validate_table) -- the kernels follow them as addresses."""
+    cq = layerlog_lib.size("mliis_layerlog_chunk_quads")
+    if chunks is None and segs is None:
+        table = _layerlog.chunk_table(sizes, cq)
+    elif chunks is None or segs is None or n is None:
+        raise MliisError("layerlog_table: chunks, segs and n go together")
+    else:
+        table = _layerlog.ChunkTable(np.asarray(chunks), np.asarray(segs), int(n))
+    try:
+        _layerlog.validate_table(table.chunks, table.segs, table.n, cq)
+    except ValueError as e:
+        raise MliisError("layerlog_table: {}".format(e)) from None
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise MliisError("layerlog_table: mliis_amd ops need device tensors (no CPU path)")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731  (validated: int32 [.., 4] arrays)
+    return LayerTable(up(table.chunks), up(table.segs), table.n)
+
+
+def layerlog_workspace(table: LayerTable) -> torch.Tensor:
+    """The workspace of one per-tensor log (int32 words; the size is the library's: one partial per chunk).  Its contents never matter
+    before a launch."""
+    return torch.zeros(layerlog_lib.size("mliis_layerlog_workspace_bytes", table.nchunks) // 4, dtype=torch.int32, device=table.chunks.device)
+
+
+def layerlog_append(x, y, table: LayerTable, ws, cursor=None, out=None, capacity=None, row_offset=0, mode="step"):
+    """Write one row of T records -- one per tensor of `table` -- into the ring `out` (device int32 [capacity, T, 8]; allocated zeroed when
+    None, `capacity` rows): per tensor {x_l2, x_absmax, y_l2, y_absmax (over the finite elements; fp32 bits), x_nonfinite, y_nonfinite
+    (uint32 counts), x_first, y_first (lowest element index of a non-finite element, 0xffffffff)} -- layerlog.RECORD_DTYPE reads them.
+    mode "step": X = x (the gradient arena), Y = y (the parameter arena); "delta": X = x - y in fp32, Y = y.  The row is
+    (cursor + row_offset) % capacity, cursor a device int32 [1] (the step log's; None counts as 0) that is read on the device and never
+    written, so the call can be captured into a HIP graph in front of steplog_append.  x / y: packed fp32 arenas of table.n floats, read
+    only; ws: layerlog_workspace(table).  Two launches on the current stream.  libmliis_layerlog.so (include/mliis_layerlog.h,
+    csrc/layerlog.hip)."""
+    if not isinstance(table, LayerTable):
+        raise MliisError("layerlog_append table: expected ops.layerlog_table(...), got {}".format(type(table)))
+    if mode not in _layerlog.MODES:
+        raise MliisError("layerlog_append: mode must be one of {}, got {!r}".format(sorted(_layerlog.MODES), mode))
+    for name, t, dt in (("x", x, torch.float32), ("y", y, torch.float32), ("ws", ws, None)) + \
+            ((("cursor", cursor, torch.int32),) if cursor is not None else ()):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MliisError("layerlog_append {}: mliis_amd ops need device tensors (no CPU path)".format(name))
+        if dt is not None and t.dtype != dt:
+            raise MliisError("layerlog_append {}: expected {} tensor, got {}".format(name, dt, t.dtype))
+        if t.device != table.chunks.device:
+            raise MliisError("layerlog_append {}: on {}, the table on {}".format(name, t.device, table.chunks.device))
+    _dense(x, y, ws, cursor, out)
+    if x.numel() != table.n or y.numel() != table.n:
+        raise MliisError("layerlog_append: x has {} elements, y {}, the table addresses {}".format(x.numel(), y.numel(), table.n))
+    if cursor is not None and cursor.numel() != 1:
+        raise MliisError("layerlog_append: cursor is one int32, got {}".format(cursor.numel()))
+    if int(row_offset) < 0 or int(row_offset) > 0xFFFFFFFF:
+        raise MliisError("layerlog_append: row_offset = {!r} (an unsigned 32-bit number)".format(row_offset))
+    need = layerlog_lib.size("mliis_layerlog_workspace_bytes", table.nchunks)
+    if ws.element_size() != 4 or ws.numel() * 4 < need:
+        raise MliisError("layerlog_append ws: {} bytes of 32-bit words needed (layerlog_workspace), got {} x {} bytes".format(
+            need, ws.numel(), ws.element_size()))
+    words = layerlog_lib.size("mliis_layerlog_record_words")
+    if out is None:
+        if capacity is None or int(capacity) < 1:
+            raise MliisError("layerlog_append: capacity = {!r} (a ring of at least one row, or out=)".format(capacity))
+        out = torch.zeros((int(capacity), table.T, words), dtype=torch.int32, device=x.device)
+    else:
+        if not torch.is_tensor(out) or not out.is_cuda or out.device != x.device or out.dtype != torch.int32 or out.dim() != 3 or \
+                out.shape[1] != table.T or out.shape[2] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
+            raise MliisError("layerlog_append out: expected a device int32 ring of shape ({}, {}, {}), got {} {}".format(
+                "capacity" if capacity is None else int(capacity), table.T, words, tuple(out.shape) if torch.is_tensor(out) else out,
+                out.dtype if torch.is_tensor(out) else type(out)))
+    _timed("layerlog_append", {}, lambda: layerlog_lib.call(
+        "mliis_layerlog_append", _layerlog.MODES[mode], _ptr(x), _ptr(y), table.n, C.c_void_p(table.chunks.data_ptr()), table.nchunks,
+        C.c_void_p(table.segs.data_ptr()), table.T, C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(out.data_ptr()), int(out.shape[0]),
+        C.c_void_p(cursor.data_ptr()) if cursor is not None else None, int(row_offset), _stream()))
     return out
 
 

@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import metaseg
-from . import steplog
+from . import layerlog, steplog
 from .spec import BN_MOMENTUM
 
 
@@ -124,7 +124,7 @@ class Gecko:
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
                  aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None, step_log: bool = False,
-                 on_divergence: str = "off"):
+                 on_divergence: str = "off", layer_log: bool = False, layer_log_interval: int = 100):
         self.learner = learner
         # step_log: the learner and every lane were built with a step log (Learner(step_log=CAPACITY)); after the task loop of a
         # meta-batch and BEFORE its all-reduce their rings are read, the records attributed to tasks by issue order and condensed into
@@ -140,6 +140,22 @@ class Gecko:
                                      for ln in [learner] + list(lanes)):
             raise ValueError("step_log=True / on_divergence={!r} need a learner (and lanes) built with a step log "
                              "(Learner(step_log=CAPACITY))".format(on_divergence))
+        # layer_log: the learner and every lane were built with the per-tensor log as well (Learner(step_log=CAPACITY, layer_log=True)).
+        # After a task's last step ||theta_task - old|| per tensor is launched into the learner's delta ring (always against `old`, with
+        # FOMAML too); the layer rings are READ only when they are used -- in every layer_log_interval-th meta-iteration, whose row
+        # (layerlog.summarize: inner_loop_layers_summary, handed to inner_loop_layers_sink) is built from them, and whenever the guard
+        # below finds a non-finite step, which is then attributed to tensors (layerlog.attribute: the row's "first_nonfinite", and
+        # DivergenceError's keyword attributes).
+        self.layer_log = bool(layer_log)
+        self.layer_log_interval = int(layer_log_interval)
+        if self.layer_log and self.layer_log_interval < 1:
+            raise ValueError("layer_log_interval must be a positive number of meta-iterations, got {}".format(layer_log_interval))
+        if self.layer_log and not (self.step_log and all(callable(getattr(ln, "read_layer_log", None)) and getattr(ln, "layer_log", False)
+                                                         for ln in [learner] + list(lanes))):
+            raise ValueError("layer_log=True needs step_log=True and a learner (and lanes) built with the per-tensor log "
+                             "(Learner(step_log=CAPACITY, layer_log=True))")
+        self.inner_loop_layers_summary = None   # the per-tensor row of the last meta-iteration that built one
+        self.inner_loop_layers_sink = None      # callable(row): train_gecko's writer of inner_loop_layers.jsonl
         self.inner_loop_summary = None   # the row of the last meta-iteration
         self.inner_loop_sink = None      # callable(row): train_gecko's writer of inner_loop.jsonl
         self.skipped_meta_iters = 0
@@ -324,6 +340,8 @@ class Gecko:
                         L.load_task(idx[0], idx[1])
                         idx = list(range(int(idx[0].shape[0])))
                     self._step(idx, j, lr)
+                if self.layer_log:
+                    self._log_delta(L, t, L.export_trainable(), old)
                 # delta += theta_task - (theta_before_last_step | theta_old)
                 L.axpby(1.0, L.export_trainable(), 1.0, delta)
                 L.axpby(-1.0, last_backup if fomaml else old, 1.0, delta)
@@ -387,6 +405,8 @@ class Gecko:
                             idx = self._device_batch(lane, idx[1], idx[0])
                         self._step(idx, j, lr, lane)
             for lane, t, _, last_backup in group:
+                if self.layer_log:
+                    self._log_delta(lane, t, lane.export_trainable(), old)
                 L.axpby(1.0, lane.export_trainable(), 1.0, delta)
                 L.axpby(-1.0, last_backup if fomaml else old, 1.0, delta)
                 L.axpby(decay ** ((meta_batch_size - 1 - t) * T), lane.export_bn(), 1.0, bn_acc)
@@ -399,6 +419,8 @@ class Gecko:
         back: a non-finite gradient has gone into the second moments)."""
         learners = [self.learner] + (self.lanes if self._lanes_in_use() else [])
         self._log_state = {id(ln): [ln, [], [], 0] for ln in learners}   # learner, its task indices, (records, dropped) chunks, pending
+        # per-tensor log: per learner the (rows, dropped) chunks and delta rows read so far, the delta-ring row of each task, rows in use
+        self._layer_state = {id(ln): {"layers": [], "deltas": [], "row": {}, "used": 0} for ln in learners} if self.layer_log else {}
         for ln in learners:
             skip = getattr(ln, "skip_step_log", None)
             if skip is not None:
@@ -421,10 +443,48 @@ class Gecko:
         if T > int(lane.step_log):
             raise ValueError("a task takes {} inner steps but the learner's step log holds {} records".format(T, lane.step_log))
         if st[3] + T > int(lane.step_log):
+            if self.layer_log:   # rows the next steps would overwrite: read with the records they belong to, before those are consumed
+                ly = self._layer_state[id(lane)]
+                ly["layers"].append(lane.read_layer_log())
+                ly["deltas"].append(lane.read_layer_deltas(range(ly["used"])))
+                ly["used"] = 0
             st[2].append(lane.read_step_log())
             st[3] = 0
         st[1].append(t)
         st[3] += T
+        if self.layer_log:   # (a task has at least one step, so the tasks between two reads never outnumber the delta ring's rows)
+            ly = self._layer_state[id(lane)]
+            ly["row"][t] = ly["used"]
+            ly["used"] += 1
+
+    def _log_delta(self, lane, t: int, theta_task, old):
+        """Task t's last step has been issued on `lane`: ||theta_task - old|| per tensor into the row _log_task gave the task."""
+        lane.layer_delta(theta_task, old, self._layer_state[id(lane)]["row"][t])
+
+    def _log_layers(self, T: int, task_records, first) -> Optional[dict]:
+        """Read every learner's layer rings (the step rings have just been read: the rows of those very steps) and build this rank's
+        per-tensor row; `first`: the summary's first non-finite {task, step} or None.  Returns the attribution of that step, or None."""
+        import numpy as np
+        names = self.learner.layer_log_names
+        step_of = dict(task_records)
+        tasks = []
+        for ln, ts, _, _ in self._log_state.values():
+            ly = self._layer_state[id(ln)]
+            chunks = ly["layers"] + [ln.read_layer_log(last_read=True)]
+            rows = np.concatenate([c[0] for c in chunks])
+            deltas = np.concatenate(ly["deltas"] + [ln.read_layer_deltas(range(ly["used"]))])
+            per_task = layerlog.split_tasks(rows, T, len(ts), sum(c[1] for c in chunks))
+            tasks += [(t, step_of[t], lay, d) for t, lay, d in zip(ts, per_task, deltas)]
+        row = layerlog.summarize(tasks, self.meta_iter)
+        found = None
+        if first:
+            _, st, lay, _ = next(x for x in tasks if x[0] == first["task"])
+            found = layerlog.attribute(names, st, lay)
+        row["first_nonfinite"] = None if found is None else dict(found, task=int(first["task"]))
+        self.inner_loop_layers_summary = row
+        if self.inner_loop_layers_sink is not None:
+            self.inner_loop_layers_sink(row)
+        return found
 
     def _log_guard(self, T: int, adam0) -> bool:
         """Read every learner's ring, build the meta-iteration's row and apply on_divergence.  True: the meta-update is to be skipped (on
@@ -446,8 +506,13 @@ class Gecko:
         if self.inner_loop_sink is not None:
             self.inner_loop_sink(row)
         first = row["first_nonfinite"] or {}
+        found = None
+        if self.layer_log and (self.meta_iter % self.layer_log_interval == 0 or row["nonfinite_steps"] > 0):
+            found = self._log_layers(T, tasks, row["first_nonfinite"])
         if bad and self.on_divergence == "abort":
-            raise steplog.DivergenceError(self.meta_iter, first.get("task"), first.get("step"), D.rank)
+            where = {} if found is None else dict(grad_nonfinite=found["grad_nonfinite"], theta_nonfinite=found["theta_nonfinite"],
+                                                  largest_grads=found["largest_grads"])
+            raise steplog.DivergenceError(self.meta_iter, first.get("task"), first.get("step"), D.rank, **where)
         if skip:
             self.skipped_meta_iters += 1
             for ln, v, t in adam0 or []:

@@ -26,12 +26,23 @@ MIN_CAPACITY = 64
 class DivergenceError(RuntimeError):
     """An inner step of this meta-iteration produced a non-finite loss, gradient or parameter (on_divergence="abort").  Raised before the
     meta-update, so the parameters -- and every checkpoint written so far -- are those of the last good iteration.
-    .meta_iter, .task, .step: where the first such step was seen on the rank that raised (task / step None: another rank saw it)."""
+    .meta_iter, .task, .step: where the first such step was seen on the rank that raised (task / step None: another rank saw it).
+    With the per-tensor log (layerlog.attribute), keyword only and None without it: .grad_nonfinite / .theta_nonfinite = (number of
+    tensors whose gradient / parameters were non-finite at that step, the first eight names), .largest_grads = the three [(name,
+    grad_absmax)] largest of the task's last finite step (None when step 0 was the bad one)."""
 
-    def __init__(self, meta_iter: int, task: Optional[int], step: Optional[int], rank: int = 0):
+    def __init__(self, meta_iter: int, task: Optional[int], step: Optional[int], rank: int = 0, *, grad_nonfinite=None,
+                 theta_nonfinite=None, largest_grads=None):
         self.meta_iter, self.task, self.step, self.rank = meta_iter, task, step, rank
+        self.grad_nonfinite, self.theta_nonfinite, self.largest_grads = grad_nonfinite, theta_nonfinite, largest_grads
         where = "task {} step {} of rank {}".format(task, step, rank) if task is not None else "a task of another rank"
-        super().__init__("inner loop diverged in meta-iteration {}: non-finite loss, gradient or parameters at {}".format(meta_iter, where))
+        msg = "inner loop diverged in meta-iteration {}: non-finite loss, gradient or parameters at {}".format(meta_iter, where)
+        for what, hit in (("gradient", grad_nonfinite), ("parameters", theta_nonfinite)):
+            if hit is not None:
+                msg += "; {} non-finite in {} tensors{}".format(what, hit[0], (": " + ", ".join(hit[1])) if hit[1] else "")
+        if largest_grads is not None:
+            msg += "; largest |grad| of the last finite step: " + ", ".join("{} {:.3g}".format(n, v) for n, v in largest_grads)
+        super().__init__(msg)
 
 
 def capacity_for(steps_per_task: int) -> int:

@@ -15,6 +15,7 @@ import numpy as np
 
 from .checkpoint import Saver
 from .reptile import Gecko
+from .layerlog import LayerLogWriter
 from .steplog import InnerLoopWriter
 
 
@@ -46,7 +47,8 @@ def train_gecko(learner, train_set, test_set, save_dir, num_classes=5, num_shots
                 meta_fn=Gecko, log_fn=print, save_checkpoint_every_n_meta_iters=100, max_checkpoints_to_keep=2, augment=False,
                 lr_scheduler=None, lr=None, save_best_seen=False, num_tasks_to_eval=100, aug_rate: Optional[float] = None, dist=None,
                 seed: int = 0, verbose: bool = True, checkpoint_format: str = "npz", aug_pool=None, lanes=(),
-                device_metrics: bool = False, inner_loop_log: bool = False, on_divergence: str = "off"):
+                device_metrics: bool = False, inner_loop_log: bool = False, on_divergence: str = "off", inner_loop_layer_log: bool = False,
+                inner_loop_layer_log_interval: int = 100):
     os.makedirs(save_dir, exist_ok=True)
     saver = Saver(max_to_keep=max_checkpoints_to_keep, fmt=checkpoint_format)
     best_saver = Saver(max_to_keep=1, fmt=checkpoint_format) if save_best_seen else None
@@ -55,13 +57,19 @@ def train_gecko(learner, train_set, test_set, save_dir, num_classes=5, num_shots
     reptile = meta_fn(learner, transductive=transductive, pre_step_op=pre_step_op, lr_scheduler=lr_scheduler, augment=augment,
                       aug_rate=aug_rate, dist=dist, seed=seed, aug_pool=aug_pool, lanes=lanes,
                       **({"device_metrics": True} if device_metrics else {}),   # (the periodic evaluations score on the device)
-                      **({"step_log": True, "on_divergence": on_divergence} if (inner_loop_log or on_divergence != "off") else {}))
+                      **({"step_log": True, "on_divergence": on_divergence}
+                         if (inner_loop_log or inner_loop_layer_log or on_divergence != "off") else {}),
+                      **({"layer_log": True, "layer_log_interval": inner_loop_layer_log_interval} if inner_loop_layer_log else {}))
     D = reptile.dist
     rank0 = D.rank == 0
     if rank0 and getattr(reptile, "step_log", False):
         # one line per meta-iteration, from rank 0's own tasks; scalars.jsonl keeps exactly its rows.  An aborting iteration's line is
         # written before DivergenceError leaves train_step -- and before the checkpoint below would have been
         reptile.inner_loop_sink = InnerLoopWriter(os.path.join(save_dir, "train")).add
+    if rank0 and getattr(reptile, "layer_log", False):
+        # the per-tensor rows (every inner_loop_layer_log_interval-th iteration, and one with a non-finite step) go to a file of their
+        # own, the tensor names once beside it; inner_loop.jsonl keeps exactly its rows
+        reptile.inner_loop_layers_sink = LayerLogWriter(os.path.join(save_dir, "train"), learner.layer_log_names).add
     writers = {"train": _ScalarWriter(os.path.join(save_dir, "train")), "test": _ScalarWriter(os.path.join(save_dir, "test"))} if rank0 else {}
     for i in range(meta_iters):
         begin = time.time()
