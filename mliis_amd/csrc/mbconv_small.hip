@@ -26,6 +26,10 @@
 // partial vectors in one wave instead of in every thread, barriers that follow a global store order LDS traffic only (the outputs
 // drain under the statistics instead of at the end of the kernel), and the 5x5 quads backward parks xhat0 in a third LDS tile instead
 // of spilling 26 registers.
+// The K*K x V filter-gradient accumulators of the backward kernel are NOT summed by six DPP levels each (as compiled that was ~16 VALU
+// instructions per value: the SLP vectoriser paired the adds into v_pk_add_f32, which takes no DPP operand): two fused DPP adds sum a
+// quad, the 16 quad sums of a wave meet in LDS, and lane (tap, row) of the same wave adds rows and wave in the pairing the six levels
+// had -- ~2.5 VALU instructions per value, the same bits (sm_quad_sum, profiles/small_map_chain.md).
 // Workgroup -> channel-group mapping keeps the groups of one 128-byte line (32 channels) on one XCD (speed only).
 // (First version -- 8 channels x 1024 threads, 128-VGPR budget, filter rows in a rolled loop, ds_bpermute reductions -- measured 24 us
 // forward / 67 us backward per 14x14x672 layer against 17 / 44 us op by op: spills and ~880 LDS instructions per wave.)
@@ -127,6 +131,20 @@ __device__ __forceinline__ float sm_wave_sum63(float v) {
   return v;                        // valid in lane 63
 }
 template <int V> __device__ __forceinline__ SmV<V> sm_wave_sum63(SmV<V> a) { SMV_FOR a.v[i] = sm_wave_sum63(a.v[i]); return a; }
+// the first two levels alone: every lane of a quad ends with (v0 + v1) + (v2 + v3).  For the K*K x V filter-gradient accumulators, whose
+// adds the SLP vectoriser would otherwise pair into v_pk_add_f32 -- a form without a DPP operand, so every level became a v_mov_b32_dpp, a
+// v_mov_b32 of its `old` value and half a packed add.  Operands and results pass through an empty asm (lone() without `volatile`, so
+// that the adds of different values still interleave and hide the DPP read-after-write wait states): each add stays one v_add_f32_dpp.
+__device__ __forceinline__ float sm_single(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ float sm_quad_sum(float v) {
+  v = sm_single(sm_dpp_add<0xB1, 0xF>(sm_single(v)));    // quad_perm [1,0,3,2]
+  v = sm_single(sm_dpp_add<0x4E, 0xF>(v));               // quad_perm [2,3,0,1]
+  return v;
+}
+template <int V> __device__ __forceinline__ SmV<V> sm_quad_sum(SmV<V> a) { SMV_FOR a.v[i] = sm_quad_sum(a.v[i]); return a; }
 
 // workgroup barrier that orders LDS traffic only: global stores issued before it stay in flight (a __syncthreads() also waits for the
 // wave's outstanding vector-memory operations, i.e. for every store issued so far)
@@ -523,6 +541,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
   // are loaded again behind the loops (26 spilled registers otherwise, each a memory round trip the next barrier waits for)
   constexpr bool PARK = K == 5 && V == 4;
   float* tileX = wred + kSmWaves * K * K * F;              // [npix] slots (PARK only): xhat0                 // [kSmWaves][K*K] slots: filter-gradient partials
+  float* qred = tileX + (PARK ? (size_t)g.npix * F : 0);   // [kSmWaves][K*K][16] slots: the quads' filter-gradient partials of each wave
   const int cq = sm_channel_group<V>(g.C);
   if (cq < 0) return;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -584,7 +603,7 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
   __syncthreads();
   constexpr int P = (K - 1) / 2;
   // ---- depthwise filter gradient: dw[ky][kx] = sum_pixels a0[h + ky - P][w + kx - P] * dz1[h][w]; window row r (image row h0 - P + r)
-  //      read once for its (j, ky = r - j) pairs; K*K accumulators, DPP wave sums, the 8 waves through LDS
+  //      read once for its (j, ky = r - j) pairs; K*K accumulators, quad sums by DPP, rows and waves through LDS
   {
     VT wacc[K * K];
 #pragma unroll
@@ -612,10 +631,28 @@ __global__ __launch_bounds__(kSmThreads) void mbconv_dw_bwd_small_k(SmallBwd p) 
         if (K == 5) __builtin_amdgcn_sched_barrier(0);
       }
     }
+    // wave sums: two DPP levels inside the quad, the 16 quad sums of a tap to LDS (one contiguous 16-slot store), then lane (tap, row)
+    // adds the four quads of its 16-lane row and two more DPP levels add the four rows -- the additions of sm_wave_sum63 in its pairing,
+    // (q0 + q1) + (q2 + q3) per row and (r0 + r1) + (r2 + r3) per wave, at 2 instead of 6 DPP adds per accumulator.  Only this wave
+    // reads what it wrote (LDS operations of a wave execute in order): no barrier.
+    float* qw = qred + (size_t)wave * (K * K * 16) * F;
 #pragma unroll
-    for (int i = 0; i < K * K; ++i) {
-      const VT v = sm_wave_sum63(wacc[i]);
-      if (lane == 63) lds_st<V>(wred, wave * (K * K) + i, v);
+    for (int i = 0; i < K * K; ++i) wacc[i] = sm_quad_sum(wacc[i]);
+    if ((lane & 3) == 0) {   // (one branch around all K*K stores: the adds above stay one block the scheduler can interleave)
+#pragma unroll
+      for (int i = 0; i < K * K; ++i) lds_st<V>(qw, i * 16 + (lane >> 2), wacc[i]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int it = 0; it < (K * K * 4 + 63) / 64; ++it) {
+      const int item = it * 64 + lane, row = item & 3;
+      const int tap = (item >> 2) < K * K ? (item >> 2) : K * K - 1;   // (whole quads of lanes beyond the last tap repeat it; not stored)
+      const VT q0 = lds_ld<V>(qw, tap * 16 + row * 4 + 0), q1 = lds_ld<V>(qw, tap * 16 + row * 4 + 1);
+      const VT q2 = lds_ld<V>(qw, tap * 16 + row * 4 + 2), q3 = lds_ld<V>(qw, tap * 16 + row * 4 + 3);
+      const VT v = sm_quad_sum(vadd(vadd(q0, q1), vadd(q2, q3)));
+      if (row == 0 && (item >> 2) < K * K) lds_st<V>(wred, wave * (K * K) + tap, v);
     }
   }
   __builtin_amdgcn_sched_barrier(0);   // (the backward-data phase's taps / window loads must not be hoisted above the K*K accumulators' end)
@@ -722,7 +759,8 @@ static bool small_geom(int N, int H, int W, int C, int k, int stride, SmallGeom*
 static size_t small_fwd_lds(const SmallGeom& g, int k) {
   return ((size_t)g.npix + (size_t)k * k + (kSmWaves + 1) * 2 + kSmThreads) * 16 + 8 * 8 + 16 * 4;
 }
-static size_t small_bwd_lds(const SmallGeom& g, int k) { return ((size_t)g.npix * (k == 5 ? 3 : 2) + (size_t)k * k + (kSmWaves + 1) * 2 + (size_t)kSmWaves * k * k) * 16; }
+// (the waves' filter-gradient sums and their 16 quad sums per tap: 5x5 at kSmMaxPix asks for 150 KB of the 160 KB of a CU)
+static size_t small_bwd_lds(const SmallGeom& g, int k) { return ((size_t)g.npix * (k == 5 ? 3 : 2) + (size_t)k * k + (kSmWaves + 1) * 2 + (size_t)kSmWaves * k * k * (1 + 16)) * 16; }
 
 // dynamic LDS above the default limit needs the function attribute: raised once per instantiation to the largest eligible request
 // (not a stream operation; done before the first launch, i.e. before any HIP-graph capture of the inner step)

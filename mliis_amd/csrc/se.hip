@@ -36,7 +36,12 @@ __device__ __forceinline__ float dot_strided(const float* __restrict__ a, int sa
 // FAST (C <= 1024, R <= 32, at most kSeFastDot phase-1 terms per thread: every layer of EfficientLab-6-3 / B0): the kernel is one latency
 // chain, so every weight a thread will need (its w1 column slice, its w2 column, the biases) is requested before phase 0 instead of
 // phase by phase -- the chain is one memory round trip + the three barriers.  Same summation order as the general form (bit-identical).
+// The 16 waves share ONE CU's address path, so the number of vector-memory instructions is what the launch costs: the register slots are
+// sized for C = 1024, R = 32, but a wave requests (and later multiplies) only the slots its C and R fill, in batches of kSeBatch behind
+// wave-uniform conditions -- the w1 slice up to the longest slice of the wave, the w2 column up to R and only in waves that own channels.
+// The terms left out were fmaf(0, w, a) on clamped duplicates of finite weights: the sums keep their bits.
 constexpr int kSeFastDot = 24;
+constexpr int kSeBatch = 4;   // slots per wave-uniform condition (one scalar branch per batch; R of the SE layers is a multiple of 4)
 template <bool FAST>
 __global__ __launch_bounds__(kSeThreads) void se_mlp_fwd_k(const float* __restrict__ s_part, int chunks, float scale,
                                                     float* __restrict__ s_out, const float* __restrict__ w1,
@@ -51,15 +56,34 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_fwd_k(const float* __restri
   const int CL = kSeThreads / R;
   const int j = t % R, cl = t / R;
   const int cnt = (cl < CL && cl < C) ? (C - cl + CL - 1) / CL : 0;
-  float w1v[FAST ? kSeFastDot : 1], w2v[FAST ? 32 : 1], b1v = 0.f, b2v = 0.f;
+  float w1v[FAST ? kSeFastDot : 1] = {}, w2v[FAST ? 32 : 1] = {}, b1v = 0.f, b2v = 0.f;
+  // (FAST) wave-uniform trip counts: the longest w1 slice of this wave is its first thread's (cnt falls with cl), and only the waves
+  // below C own a channel of the last phase
+  const int wave_u = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int cl_u = (wave_u * 64) / R;
+  const int cnt_u = (cl_u < CL && cl_u < C) ? (C - cl_u + CL - 1) / CL : 0;
+  const bool own_u = wave_u * 64 < C;
   if constexpr (FAST) {
     const int cc = t < C ? t : C - 1;
 #pragma unroll
-    for (int i = 0; i < kSeFastDot; ++i) w1v[i] = w1[(long long)(cl + (i < cnt ? i : 0) * CL < C ? cl + (i < cnt ? i : 0) * CL : 0) * R + j];
+    for (int i0 = 0; i0 < kSeFastDot; i0 += kSeBatch) {
+      if (i0 < cnt_u) {
 #pragma unroll
-    for (int k = 0; k < 32; ++k) w2v[k] = w2[(long long)(k < R ? k : R - 1) * C + cc];
-    b1v = b1[t < R ? t : 0];
-    b2v = b2[cc];
+        for (int i = i0; i < i0 + kSeBatch; ++i)
+          w1v[i] = w1[(long long)(cl + (i < cnt ? i : 0) * CL < C ? cl + (i < cnt ? i : 0) * CL : 0) * R + j];
+      }
+    }
+    if (own_u) {
+#pragma unroll
+      for (int k0 = 0; k0 < 32; k0 += kSeBatch) {
+        if (k0 < R) {
+#pragma unroll
+          for (int k = k0; k < k0 + kSeBatch; ++k) w2v[k] = w2[(long long)(k < R ? k : R - 1) * C + cc];
+        }
+      }
+      b2v = b2[cc];
+    }
+    if (wave_u == 0) b1v = b1[t < R ? t : 0];
   }
   for (int c = t; c < C; c += kSeThreads) {
     const float* pp = s_part + ((long long)n * chunks) * C + c;
@@ -80,7 +104,12 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_fwd_k(const float* __restri
   float part = 0.f;
   if constexpr (FAST) {
 #pragma unroll
-    for (int i = 0; i < kSeFastDot; ++i) part = fmaf(i < cnt ? sn[cl + i * CL] : 0.f, w1v[i], part);
+    for (int i0 = 0; i0 < kSeFastDot; i0 += kSeBatch) {
+      if (i0 < cnt_u) {
+#pragma unroll
+        for (int i = i0; i < i0 + kSeBatch; ++i) part = fmaf(i < cnt ? sn[cl + i * CL] : 0.f, w1v[i], part);
+      }
+    }
   } else {
     if (cnt > 0) part = dot_strided<8>(sn + cl, CL, w1 + (long long)cl * R + j, (long long)CL * R, cnt);
   }
@@ -105,7 +134,12 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_fwd_k(const float* __restri
     if (t < C) {
       float a = b2v;
 #pragma unroll
-      for (int k = 0; k < 32; ++k) a = fmaf(k < R ? sh[k] : 0.f, w2v[k], a);
+      for (int k0 = 0; k0 < 32; k0 += kSeBatch) {
+        if (k0 < R) {
+#pragma unroll
+          for (int k = k0; k < k0 + kSeBatch; ++k) a = fmaf(k < R ? sh[k] : 0.f, w2v[k], a);
+        }
+      }
       gate[(long long)n * C + t] = sigmoid_f(a);
     }
     return;
@@ -134,6 +168,9 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_fwd_k(const float* __restri
 // FAST (C <= 1024, R <= 32): one channel per thread; the w2 rows of this wave, the w1 column of this thread and hpre are requested
 // before the gate gradient is folded (the general form pays a round trip per batch of eight and one more per row for hpre), and an
 // image's chunk partials are folded by kSeThreads / C thread groups side by side (chunk b -> group b mod G, groups summed in order).
+// As in the forward kernel a wave requests only what its C and R fill (wave-uniform conditions, still all before the first wait): a w2
+// row only where wave + 16 r < R and only its 64-channel pieces below C (in pairs), the w1 column up to R (batches of kSeBatch) and the
+// row-group partials of the gate gradient only in waves that own channels.  Same terms in the same order as before, minus fmaf(0, w, a).
 template <bool FAST>
 __global__ __launch_bounds__(kSeThreads) void se_mlp_bwd_k(const float* __restrict__ dgate, int dgate_groups, int HW,
                                                     const float* __restrict__ gate,
@@ -151,18 +188,34 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_bwd_k(const float* __restri
   if constexpr (FAST) {
     const int cc = t < C ? t : C - 1;
     const float gte = gate[(long long)n * C + cc];
-    float w2v[2][16], w1v[32], hp[2];
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const bool own_u = wave_u * 64 < C;   // this wave owns channels (t < C somewhere in it)
+    float w2v[2][16] = {}, w1v[32] = {}, hp[2] = {0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-      const int jj = wave + 16 * r < R ? wave + 16 * r : R - 1;
-      hp[r] = hpre[(long long)n * R + jj];
+      const int jj = wave_u + 16 * r;
+      if (jj < R) {
+        hp[r] = hpre[(long long)n * R + jj];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) w2v[r][u] = w2[(long long)jj * C + (lane + 64 * u < C ? lane + 64 * u : C - 1)];
+        for (int u0 = 0; u0 < 16; u0 += 2) {
+          if (64 * u0 < C) {
+#pragma unroll
+            for (int u = u0; u < u0 + 2; ++u) w2v[r][u] = w2[(long long)jj * C + (lane + 64 * u < C ? lane + 64 * u : C - 1)];
+          }
+        }
+      }
     }
+    if (own_u) {
 #pragma unroll
-    for (int k = 0; k < 32; ++k) {
-      const int kk = k < R ? k : R - 1;
-      w1v[k] = w1t != nullptr ? w1t[(long long)kk * C + cc] : w1[(long long)cc * R + kk];
+      for (int k0 = 0; k0 < 32; k0 += kSeBatch) {
+        if (k0 < R) {
+#pragma unroll
+          for (int k = k0; k < k0 + kSeBatch; ++k) {
+            const int kk = k < R ? k : R - 1;
+            w1v[k] = w1t != nullptr ? w1t[(long long)kk * C + cc] : w1[(long long)cc * R + kk];
+          }
+        }
+      }
     }
     float dg = 0.f;
     if (sums != nullptr) {
@@ -200,7 +253,7 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_bwd_k(const float* __restri
         for (int k = 1; k < 5; ++k) sd2[k * C + t] = p[k];
       }
     } else if (dgate_groups > 0) {
-      for (int k = g_lo; k <= g_hi; k += 16) {
+      for (int k = g_lo; own_u && k <= g_hi; k += 16) {
         float v[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -226,7 +279,12 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_bwd_k(const float* __restri
       if (jj < R) {
         float p = 0.f;
 #pragma unroll
-        for (int u = 0; u < 16; ++u) p = fmaf(lane + 64 * u < C ? sd2[lane + 64 * u] : 0.f, w2v[r][u], p);
+        for (int u0 = 0; u0 < 16; u0 += 2) {
+          if (64 * u0 < C) {
+#pragma unroll
+            for (int u = u0; u < u0 + 2; ++u) p = fmaf(lane + 64 * u < C ? sd2[lane + 64 * u] : 0.f, w2v[r][u], p);
+          }
+        }
         p = wave_sum(p);
         if (lane == 0) {
           const float d = p * swish_grad_f(hp[r]);
@@ -239,7 +297,12 @@ __global__ __launch_bounds__(kSeThreads) void se_mlp_bwd_k(const float* __restri
     if (t < C) {
       float a = 0.f;
 #pragma unroll
-      for (int k = 0; k < 32; ++k) a = fmaf(k < R ? sd1[k] : 0.f, w1v[k], a);
+      for (int k0 = 0; k0 < 32; k0 += kSeBatch) {
+        if (k0 < R) {
+#pragma unroll
+          for (int k = k0; k < k0 + kSeBatch; ++k) a = fmaf(k < R ? sd1[k] : 0.f, w1v[k], a);
+        }
+      }
       const float ca = a * inv_hw;
       chan_add[(long long)n * C + t] = ca;
       if (sums != nullptr) {   // {sum g, sum g xhat} of this image, g = (da2 * gate + chan_add) * swish'
