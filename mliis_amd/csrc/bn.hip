@@ -24,6 +24,106 @@ constexpr int kBatch = 4;        // rows per thread whose loads are issued befor
 constexpr int kPoolRows = 128;   // rows per pooling chunk of bn_apply_fused (one batch per thread)
 constexpr int kStatsPartialTarget = 256;   // workgroups of mliis_bn_stats_partial (= partial blocks its consumer folds)
 
+// ---------------------------------------------------------------------------------------------------------------
+// Compile-time forms.  Most launches of this file are 5-10 us on 1-20 MB: a thread handles four rows or a few more, and what the
+// launch costs is the length of the instruction path around those rows, not bytes.  So every flag combination the training passes
+// issue has an instance of its own whose row body is straight-line code (FORM >= 0: a mask of the flag bits below), and one
+// run-time-flag instance (kFormGeneric) serves every other combination the C ABI allows.  The routing functions
+// (bn_apply_form / bn_bwd_form / bn_bwd_reduce_form) are the only place that decides which instance a call takes.
+//
+// A compile-time form also addresses its tensors with a wave-uniform buffer resource and a 32-bit byte offset per lane (Rows<T, true>)
+// instead of a 64-bit multiply-add per tensor and row; a row outside the block's range takes the out-of-range offset (the load
+// returns zeros and moves no data, the store is dropped) instead of a branch.  The host sends a call with a tensor extent of 2^31
+// bytes or more to the generic instance.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kFormGeneric = -1;
+enum : int { kAPre = 1, kAPost = 2, kAIsc = 4, kARes = 8, kAPool = 16 };                                            // bn_apply_fused_k
+enum : int { kBPre = 1, kBPost = 2, kBIs = 4, kBCs = 8, kBCa = 16, kBSkipW = 32, kBSkipA = 64, kBDxsum = 128 };     // bn_bwd_apply_fused_k
+constexpr int kBRowMask = kBPre | kBPost | kBIs | kBCs | kBCa;   // the bits BnBwdCommon (shared with the reduce pass) reads
+constexpr int bwd_row_form(int form) { return form < 0 ? kFormGeneric : (form & kBRowMask); }
+
+// The optional stages of a row (swish, per-image scale, ...) sit in basic blocks of their own when their flags are run-time values, so
+// the compiler never contracts a multiply at the end of one stage with an add at the start of the next.  With compile-time flags the
+// stages meet in one block and it would (fma): other bits.  A stage's result passes through own4() -- no instruction, but the
+// optimiser cannot look through it -- so every form computes what the run-time-flag form computes.
+__device__ __forceinline__ float4 own4(float4 v) {
+  asm("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+  return v;
+}
+
+typedef unsigned bn_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned bn_u32x2 __attribute__((ext_vector_type(2)));
+constexpr unsigned kBnOob = 0xFFFFFFF0u;   // beyond num_records: a load returns zeros and moves no data, a store is dropped
+// (the pointer halves go through readfirstlane so that the descriptor is provably wave-uniform: no waterfall loop around the accesses)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t bn_rsrc(const void* p) {
+  const unsigned long long u = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x80000000u, 0x00020000);
+}
+template <typename T> __device__ __forceinline__ float4 bn_buf_ldq(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  if constexpr (sizeof(T) == 4) {
+    const bn_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+    return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
+  } else {
+    const bn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
+    return unpack_bf16x4(make_uint2(u.x, u.y));
+  }
+}
+template <typename T> __device__ __forceinline__ void bn_buf_stq(__amdgpu_buffer_rsrc_t r, unsigned off, const float4 v) {
+  if constexpr (sizeof(T) == 4) {
+    bn_u32x4 u;
+    u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y); u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
+    __builtin_amdgcn_raw_buffer_store_b128(u, r, (int)off, 0, 0);
+  } else {
+    const uint2 pk = pack_bf16x4(v);
+    bn_u32x2 u;
+    u.x = pk.x; u.y = pk.y;
+    __builtin_amdgcn_raw_buffer_store_b64(u, r, (int)off, 0, 0);
+  }
+}
+
+// A [rows, ld] tensor of T as a row kernel addresses it: quad (row, c), c in elements.  `ok` false: the access is not wanted (a row
+// outside the block's range).  Wide form: the pointer arithmetic these kernels have always done -- an unwanted load reads the valid
+// `shadow` row and is ignored, stores are the caller's to guard.  Narrow form: the buffer resource.
+template <typename T, bool NARROW>
+struct Rows {
+  typedef long long Row;
+  const T* p;
+  int ld;
+  __device__ __forceinline__ Rows(const T* p_, int ld_) : p(p_), ld(ld_) {}
+  __device__ __forceinline__ float4 load(long long row, int c, bool ok = true, long long shadow = 0) const { return ldq(p + (ok ? row : shadow) * ld + c); }
+  __device__ __forceinline__ void store(long long row, int c, const float4 v, bool ok = true) const {
+    if (ok) stq(const_cast<T*>(p) + row * ld + c, v);
+  }
+};
+template <typename T>
+struct Rows<T, true> {
+  typedef int Row;
+  __amdgpu_buffer_rsrc_t r;
+  unsigned ldb;
+  __device__ __forceinline__ Rows(const T* p_, int ld_) : r(bn_rsrc(p_)), ldb((unsigned)ld_ * (unsigned)sizeof(T)) {}
+  __device__ __forceinline__ unsigned off(long long row, int c) const { return (unsigned)row * ldb + (unsigned)c * (unsigned)sizeof(T); }
+  __device__ __forceinline__ float4 load(long long row, int c, bool ok = true, long long = 0) const { return bn_buf_ldq<T>(r, ok ? off(row, c) : kBnOob); }
+  __device__ __forceinline__ void store(long long row, int c, const float4 v, bool ok = true) const { bn_buf_stq<T>(r, ok ? off(row, c) : kBnOob, v); }
+};
+// one float per lane through the same kind of view ([n] vectors: the per-image scale)
+template <bool NARROW>
+struct Vec1 {
+  const float* p;
+  __device__ __forceinline__ Vec1(const float* p_) : p(p_) {}
+  __device__ __forceinline__ float load(int i, bool ok = true) const { return p[ok ? i : 0]; }
+};
+template <>
+struct Vec1<true> {
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ Vec1(const float* p_) : r(bn_rsrc(p_)) {}
+  __device__ __forceinline__ float load(int i, bool ok = true) const {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, ok ? (int)((unsigned)i * 4u) : (int)kBnOob, 0, 0));
+  }
+};
+// the host side of the rule: every [rows, ld] tensor of a call stays below 2^31 bytes
+static inline bool narrow_extent(long long rows, long long ld, size_t elem) { return rows * ld * (long long)elem < (1LL << 31); }
+
 // Streaming geometry shared by the column reductions and the BN apply kernels: grid = (row chunks, ceil(C/32)[, segments]);
 // a block owns 32 channels x rows_per_block rows, its 256 threads = 8 channel quads x 32 row lanes.  Small maps are latency-bound
 // (a handful of waves per CU), so every thread issues the loads of kBatch rows before it touches any of them: the per-launch
@@ -49,9 +149,28 @@ static inline ColGeom col_geom(long long rows_per_seg, int C, int nseg, int targ
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Generic partial column reduction.  Op: Raw load(seg,row,c) then eval(seg,row,c,raw,out[NV]).
+// Generic partial column reduction.  Op: View view(seg), Raw load(view,seg,row,c), Ctx ctx(c), then eval(ctx,raw,out[NV]).
 // part layout: [seg][blk][v][C]
 // ---------------------------------------------------------------------------------------------------------------
+// One row into the accumulators.  An op whose second value is a product accumulates it with an explicit fma (Op::kAccum): the
+// compiler has always contracted `acc + p * q` here, and whether it does must not depend on what else it finds to pack in a form.
+template <class Op>
+__device__ __forceinline__ void col_accum(const Op& op, const typename Op::Ctx& ctx, const typename Op::Raw& raw, float4 (&acc)[Op::NV]) {
+  if constexpr (Op::kAccum) {
+    op.accum(ctx, raw, acc);
+  } else {
+    float4 vals[Op::NV];
+    op.eval(ctx, raw, vals);
+#pragma unroll
+    for (int v = 0; v < Op::NV; ++v) acc[v] = f4add(acc[v], vals[v]);
+  }
+}
+// swish'(x) with the contraction the compiler has always made in this file written out: s * fma(x, 1 - s, 1)
+__device__ __forceinline__ float bn_swish_grad(float x) {
+  const float s = sigmoid_f(x);
+  return s * fmaf(x, 1.0f - s, 1.0f);
+}
+
 template <class Op>
 __global__ __launch_bounds__(kColThreads) void colreduce_partial_k(Op op, int rows_per_seg, int C, int rows_per_block, int nblk,
                                                                     float* __restrict__ part) {
@@ -71,42 +190,34 @@ __global__ __launch_bounds__(kColThreads) void colreduce_partial_k(Op op, int ro
     if (r1 > rows_per_seg) r1 = rows_per_seg;
     const long long base = (long long)seg * rows_per_seg;
     int r = r0 + rl;
+    const typename Op::View vw = op.view(seg);   // how the op addresses its tensors (Rows<>), built once per thread
     // first batch: its loads are issued before the per-channel constants are fetched (one memory round trip on small maps)
     typename Op::Raw first[kBatch];
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
       const int ru = r + u * kRowLanes;
-      op.load(seg, base + (ru < r1 ? ru : r0), c, first[u]);
+      op.load(vw, seg, base + (ru < r1 ? ru : r0), c, first[u]);
     }
     const typename Op::Ctx ctx = op.ctx(c);   // per-channel constants, loaded once per thread
 #pragma unroll
     for (int u = 0; u < kBatch; ++u)
       if (r + u * kRowLanes < r1) {
-        float4 vals[NV];
-        op.eval(ctx, first[u], vals);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) acc[v] = f4add(acc[v], vals[v]);
+        col_accum(op, ctx, first[u], acc);
       }
     r += kBatch * kRowLanes;
     for (; r + (kBatch - 1) * kRowLanes < r1; r += kBatch * kRowLanes) {
       typename Op::Raw raw[kBatch];
 #pragma unroll
-      for (int u = 0; u < kBatch; ++u) op.load(seg, base + r + u * kRowLanes, c, raw[u]);
+      for (int u = 0; u < kBatch; ++u) op.load(vw, seg, base + r + u * kRowLanes, c, raw[u]);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        float4 vals[NV];
-        op.eval(ctx, raw[u], vals);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) acc[v] = f4add(acc[v], vals[v]);
+        col_accum(op, ctx, raw[u], acc);
       }
     }
     for (; r < r1; r += kRowLanes) {
       typename Op::Raw raw;
-      op.load(seg, base + r, c, raw);
-      float4 vals[NV];
-      op.eval(ctx, raw, vals);
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] = f4add(acc[v], vals[v]);
+      op.load(vw, seg, base + r, c, raw);
+      col_accum(op, ctx, raw, acc);
     }
   }
   // 8 row lanes of a wave share a channel quad: butterfly over lane bits 3..5, then the 4 waves through LDS (fixed order)
@@ -150,22 +261,38 @@ static int launch_colreduce(Op op, long long rows_per_seg, int C, int nseg, floa
 // ---------------------------------------------------------------------------------------------------------------
 // BN statistics
 // ---------------------------------------------------------------------------------------------------------------
+template <int PRE, bool NARROW>   // PRE: 0 / 1, or kFormGeneric for the run-time flag
 struct StatsOp {
   static constexpr int NV = 2;
+  static constexpr bool kAccum = true;
   const float* x;
   int ld;
   int pre_swish;
   typedef float4 Raw;
   struct Ctx {};
+  typedef Rows<float, NARROW> View;
+  __device__ __forceinline__ View view(int) const { return View(x, ld); }
   __device__ __forceinline__ Ctx ctx(int) const { return Ctx(); }
-  __device__ __forceinline__ void load(int, long long row, int c, Raw& r) const { r = ld4(x + row * ld + c); }
+  __device__ __forceinline__ void load(const View& vw, int, long long row, int c, Raw& r) const { r = vw.load(row, c); }
   __device__ __forceinline__ void eval(const Ctx&, const Raw& r, float4* o) const {
     float4 v = r;
-    if (pre_swish) v = make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w));
+    if (PRE < 0 ? pre_swish != 0 : PRE != 0) v = own4(make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w)));
     o[0] = v;
     o[1] = f4mul(v, v);
   }
+  __device__ __forceinline__ void accum(const Ctx& k, const Raw& r, float4 (&acc)[NV]) const {
+    float4 o[NV];
+    eval(k, r, o);
+    acc[0] = f4add(acc[0], o[0]);
+    acc[1] = f4fma(o[0], o[0], acc[1]);
+  }
 };
+// the one routing decision of the statistics pass
+template <class F>
+static int stats_route(const float* x, int ldx, long long rows, int pre_swish, F&& go) {
+  if (!narrow_extent(rows, ldx, sizeof(float))) return go(StatsOp<kFormGeneric, false>{x, ldx, pre_swish});
+  return pre_swish ? go(StatsOp<1, true>{x, ldx, 1}) : go(StatsOp<0, true>{x, ldx, 0});
+}
 
 __global__ __launch_bounds__(256) void bn_stats_finalize_k(const float* __restrict__ part, int nblk, int C, double inv_n, float eps,
                                                            float one_minus_momentum, float ema_var_factor,
@@ -234,16 +361,23 @@ struct BnApplyAlt {
 // (<= 168 VGPRs: three workgroups per CU.  With the 16-block fold batches of an earlier form the kernel needed 216 and two fitted -- the
 //  600-1568-workgroup launches of the large maps ran in two or three rounds with few waves in flight; stamps build, round 3)
 // TX / TY: storage types of x and y (float | bf16s: the expanded tensors of `--precision bf16-storage`; the pair form is float only)
-// RES / ISC: a residual operand / a per-image scale exist.  Compile-time: without them a row is ONE load instruction instead of three
-// (the shadow loads that used to stand in for absent operands were L1 hits, but these launches are bound by the number of
-// vector-memory instructions, not by bytes -- profiles/r04_notes.md).
-template <typename TX, typename TY, bool RES = true, bool ISC = true>
+// FORM: a mask of kAPre | kAPost | kAIsc | kARes | kAPool fixed at compile time, or kFormGeneric (flags read from the arguments; the
+// operands that may be absent are then loaded from a valid shadow and ignored, so no branch stands around a load).  Without a
+// residual / a per-image scale a row is ONE load instruction instead of three: these launches are bound by the number of
+// vector-memory instructions, not by bytes -- profiles/r04_notes.md.
+template <typename TX, typename TY, int FORM>
 __global__ __launch_bounds__(256, 3) void bn_apply_fused_k(const TX* __restrict__ x, int ldx, TY* __restrict__ y, int ldy,
                                                         long long rows, int C, int rows_per_img, BnFold f,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int pre_swish, int post_swish, const float* __restrict__ img_scale,
                                                         const float* __restrict__ res, int ldr, int rows_per_block,
                                                         float* __restrict__ pool_part, int pool_chunks, BnApplyAlt alt) {
+  constexpr bool kGen = FORM < 0, NARROW = !kGen;
+  constexpr bool RES = kGen || (FORM & kARes) != 0, ISC = kGen || (FORM & kAIsc) != 0;   // the operand's loads exist
+  const bool pre = kGen ? pre_swish != 0 : (FORM & kAPre) != 0, post = kGen ? post_swish != 0 : (FORM & kAPost) != 0;
+  const bool has_isc = kGen ? img_scale != nullptr : ISC, has_res = kGen ? res != nullptr : RES;
+  const bool pooling = kGen ? pool_part != nullptr : (FORM & kAPool) != 0;
+  typedef typename Rows<TX, NARROW>::Row Row;   // (narrow: every row index fits an int -- the extents are below 2^31 bytes)
   if (blockIdx.z == 1) {   // (uniform)
     x = reinterpret_cast<const TX*>(alt.x);
     y = reinterpret_cast<TY*>(alt.y);
@@ -259,90 +393,99 @@ __global__ __launch_bounds__(256, 3) void bn_apply_fused_k(const TX* __restrict_
   const bool cok = c0 + q * 4 < C;
   const int c = cok ? c0 + q * 4 : 0;   // surplus lanes shadow channel 0 with an empty row range (they stay for the reductions)
   // row range: plain chunks of rows_per_block, or (pooling) chunk (blockIdx.y % pool_chunks) of image (blockIdx.y / pool_chunks)
-  long long r0 = (long long)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block;
-  if (pool_part != nullptr) {
+  Row r0 = (Row)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block;
+  if (pooling) {
     const int img = blockIdx.y / pool_chunks, ch = blockIdx.y - img * pool_chunks;
-    r0 = (long long)img * rows_per_img + (long long)ch * rows_per_block;
+    r0 = (Row)img * rows_per_img + (Row)ch * rows_per_block;
     r1 = r0 + rows_per_block;
-    if (r1 > (long long)(img + 1) * rows_per_img) r1 = (long long)(img + 1) * rows_per_img;
+    if (r1 > (Row)(img + 1) * rows_per_img) r1 = (Row)(img + 1) * rows_per_img;
   }
-  if (r1 > rows) r1 = rows;
+  if (r1 > (Row)rows) r1 = (Row)rows;
   if (!cok) r1 = r0;
   // The first batch of rows does not depend on the statistics: fetch it BEFORE folding them, so the small-map launches (one batch
   // per thread) pay one memory round trip instead of two.
-  long long r = r0 + rl;
-  const float* rbase = res != nullptr ? res : gamma;   // no residual: the loads shadow gamma (ignored later) -- no branch around them
-  const int rld = res != nullptr ? ldr : 0;
-  const int rcol = res != nullptr ? c : 0;
-  const float* isb = img_scale != nullptr ? img_scale : gamma;   // (absent: shadows gamma, ignored)
+  Row r = r0 + rl;
+  const Rows<TX, NARROW> X(x, ldx);
+  const Rows<TY, NARROW> Y(y, ldy);
+  // no residual (generic form only): the loads shadow gamma (ignored later) -- no branch around them
+  const Rows<float, NARROW> R(has_res ? res : gamma, has_res ? ldr : 0);
+  const int rcol = has_res ? c : 0;
+  const Vec1<NARROW> IS(has_isc ? img_scale : gamma);   // (absent: shadows gamma, ignored)
+  auto fetch = [&](Row rw, bool ok, float4& v, float4& rv, float& isc) {
+    v = X.load(rw, c, ok);
+    rv = RES ? R.load(rw, rcol, ok) : f4zero();
+    isc = ISC ? IS.load(has_isc ? (int)rw / rows_per_img : 0, ok) : 1.f;
+  };
   float4 v0[kBatch], rv0[kBatch];
   float is0[kBatch];
 #pragma unroll
-  for (int u = 0; u < kBatch; ++u) {
-    const long long ru = r + u * kRowLanes;
-    const long long rr = ru < r1 ? ru : 0;
-    v0[u] = ldq(x + rr * ldx + c);
-    rv0[u] = RES ? ld4(rbase + rr * rld + rcol) : f4zero();
-    is0[u] = ISC ? isb[img_scale != nullptr ? (int)rr / rows_per_img : 0] : 1.f;
-  }
+  for (int u = 0; u < kBatch; ++u) fetch(r + u * kRowLanes, r + u * kRowLanes < r1, v0[u], rv0[u], is0[u]);
   const float4 g = ld4(gamma + c), b = ld4(beta + c);   // (before the fold: they do not depend on it)
   double s, ss;
   // (16 partial blocks per lane and round trip when a producer left many: one round per 512 instead of per 256)
   fold32<8>(f.part, f.nblk, C, c0, smd, s, ss);
+  double var = 0.0;
+  float mf = 0.f, rf = 0.f;
   if (t < 32) {
-    double m = s * f.inv_n;
-    double var = ss * f.inv_n - m * m;
+    const double m = s * f.inv_n;
+    var = ss * f.inv_n - m * m;
     if (var < 0.0) var = 0.0;
-    const float mf = (float)m, rf = (float)(1.0 / sqrt(var + (double)f.eps));
+    mf = (float)m;
+    rf = (float)(1.0 / sqrt(var + (double)f.eps));
     s_mean[t] = mf;
     s_rstd[t] = rf;
-    const int cc = c0 + t;
-    if (blockIdx.y == 0 && cc < C) {
-      f.mean[cc] = mf;
-      f.rstd[cc] = rf;
-      if (f.moving_mean != nullptr) {
-        const float mm = f.moving_mean[cc], mv = f.moving_var[cc];
-        f.moving_mean[cc] = mm - (mm - mf) * f.one_minus_momentum;
-        f.moving_var[cc] = mv - (mv - (float)(var * (double)f.ema_var_factor)) * f.one_minus_momentum;
-      }
-    }
   }
   __syncthreads();
+  // (after the barrier: the other 224 threads do not wait for the first row of blocks to publish the statistics)
+  if (t < 32 && blockIdx.y == 0 && c0 + t < C) {
+    const int cc = c0 + t;
+    f.mean[cc] = mf;
+    f.rstd[cc] = rf;
+    if (f.moving_mean != nullptr) {
+      const float mm = f.moving_mean[cc], mv = f.moving_var[cc];
+      f.moving_mean[cc] = mm - (mm - mf) * f.one_minus_momentum;
+      f.moving_var[cc] = mv - (mv - (float)(var * (double)f.ema_var_factor)) * f.one_minus_momentum;
+    }
+  }
   const float4 m = ld4(s_mean + q * 4), rs = ld4(s_rstd + q * 4);
   float4 pool = f4zero();   // sum of this thread's outputs (squeeze-excite pooling, training)
-  auto finish = [&](long long rw, float4 v, float4 rv, float isc) {
-    if (pre_swish) v = make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w));
+  // ok: the row is inside the block's range (narrow forms run the rows of the first batch without a branch: an unwanted row
+  // computes on the zeros its loads returned, its store is dropped and it adds +0 to the pool sum, which never holds -0)
+  auto finish = [&](Row rw, bool ok, float4 v, float4 rv, float isc) {
+    if (pre) v = own4(make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w)));
     float4 o;
     o.x = fmaf((v.x - m.x) * rs.x, g.x, b.x);
     o.y = fmaf((v.y - m.y) * rs.y, g.y, b.y);
     o.z = fmaf((v.z - m.z) * rs.z, g.z, b.z);
     o.w = fmaf((v.w - m.w) * rs.w, g.w, b.w);
-    if (post_swish) o = make_float4(swish_f(o.x), swish_f(o.y), swish_f(o.z), swish_f(o.w));
-    if (img_scale != nullptr) o = f4scale(o, isc);
-    if (res != nullptr) o = f4add(o, rv);
+    if (post) o = own4(make_float4(swish_f(o.x), swish_f(o.y), swish_f(o.z), swish_f(o.w)));
+    if (has_isc) o = own4(f4scale(o, isc));
+    if (has_res) o = f4add(o, rv);
     o = stored_value(y, o);   // (bf16 storage: the pooled means see what the consumers will read)
-    pool = f4add(pool, o);
-    stq(y + rw * ldy + c, o);
+    if (pooling) pool = f4add(pool, ok ? o : f4zero());
+    Y.store(rw, c, o, ok);
   };
 #pragma unroll
-  for (int u = 0; u < kBatch; ++u)
-    if (r + u * kRowLanes < r1) finish(r + u * kRowLanes, v0[u], rv0[u], is0[u]);
+  for (int u = 0; u < kBatch; ++u) {
+    const bool ok = r + u * kRowLanes < r1;
+    if (NARROW || ok) finish(r + u * kRowLanes, ok, v0[u], rv0[u], is0[u]);
+  }
   r += kBatch * kRowLanes;
   for (; r + (kBatch - 1) * kRowLanes < r1; r += kBatch * kRowLanes) {
     float4 v[kBatch], rv[kBatch];
     float is[kBatch];
 #pragma unroll
-    for (int u = 0; u < kBatch; ++u) {
-      v[u] = ldq(x + (r + u * kRowLanes) * ldx + c);
-      rv[u] = RES ? ld4(rbase + (r + u * kRowLanes) * rld + rcol) : f4zero();
-      is[u] = ISC ? isb[img_scale != nullptr ? (int)(r + u * kRowLanes) / rows_per_img : 0] : 1.f;
-    }
+    for (int u = 0; u < kBatch; ++u) fetch(r + u * kRowLanes, true, v[u], rv[u], is[u]);
 #pragma unroll
-    for (int u = 0; u < kBatch; ++u) finish(r + u * kRowLanes, v[u], rv[u], is[u]);
+    for (int u = 0; u < kBatch; ++u) finish(r + u * kRowLanes, true, v[u], rv[u], is[u]);
   }
-  for (; r < r1; r += kRowLanes)
-    finish(r, ldq(x + r * ldx + c), RES ? ld4(rbase + r * rld + rcol) : f4zero(), ISC ? isb[img_scale != nullptr ? (int)r / rows_per_img : 0] : 1.f);
-  if (pool_part == nullptr) return;   // (uniform)
+  for (; r < r1; r += kRowLanes) {
+    float4 v, rv;
+    float is;
+    fetch(r, true, v, rv, is);
+    finish(r, true, v, rv, is);
+  }
+  if (!pooling) return;   // (uniform)
   // pooled partial of this block: butterfly over the 8 row lanes of a wave that share a quad, then the 4 waves through LDS
 #pragma unroll
   for (int off = 8; off < 64; off <<= 1) {
@@ -389,8 +532,14 @@ static inline void bn_bwd_grid(long long rows, int C, int* gx, int* gy, int* row
 }
 
 // upstream gradient seen by the BN output: dy * img_scale[n] * chan_scale[n,c] + chan_add[n,c]
-template <bool SE, typename T = float>   // SE: per-image vectors (drop-connect scale, squeeze-excite gate / pooled gradient) are present;
-struct BnBwdCommon {                       // T: storage type of x and dy (and of the dx the apply kernel writes)
+// RF: a mask of kBPre | kBPost | kBIs | kBCs | kBCa fixed at compile time, or kFormGeneric: the flags are the struct's run-time
+//     fields, and the per-image vectors (drop-connect scale, squeeze-excite gate / pooled gradient) are all loaded -- absent ones
+//     from a valid dummy.  T: storage type of x and dy (and of the dx the apply kernel writes)
+template <int RF, typename T = float>
+struct BnBwdCommon {
+  static constexpr bool kGen = RF < 0, NARROW = !kGen;
+  static constexpr bool IS = kGen || (RF & kBIs) != 0, CS = kGen || (RF & kBCs) != 0, CA = kGen || (RF & kBCa) != 0;   // the loads exist
+  static constexpr bool SE = IS || CS || CA;
   const T* x;   // conv output saved in forward (pre-BN, pre-swish if pre_swish)
   int ldx;
   const T* dy;
@@ -407,16 +556,31 @@ struct BnBwdCommon {                       // T: storage type of x and dy (and o
   const float* chan_add;    // [N,C] or null      (squeeze-excite pooled-gradient / HW)
   // everything a row needs from memory, fetched together (no load is left inside finish(): the per-image vectors used to cost
   // one dependent round trip per row)
+  __device__ __forceinline__ bool pre() const { return kGen ? pre_swish != 0 : (RF & kBPre) != 0; }
+  __device__ __forceinline__ bool post() const { return kGen ? post_swish != 0 : (RF & kBPost) != 0; }
+  __device__ __forceinline__ bool has_is() const { return kGen ? img_scale != nullptr : IS; }
+  __device__ __forceinline__ bool has_cs() const { return kGen ? chan_scale != nullptr : CS; }
+  __device__ __forceinline__ bool has_ca() const { return kGen ? chan_add != nullptr : CA; }
   struct Raw { float4 x, g, cs, ca; float is; };
-  __device__ __forceinline__ void load_raw(long long row, int c, Raw& r) const {
-    r.x = ldq(x + row * ldx + c);
-    r.g = ldq(dy + row * lddy + c);
+  struct View {   // how a thread addresses the tensors (built once per thread)
+    Rows<T, NARROW> X, G;
+    Rows<float, NARROW> CSV, CAV;
+    Vec1<NARROW> ISV;
+  };
+  __device__ __forceinline__ View view() const {
+    // absent vectors (generic form) read a valid dummy (the mean vector) and are ignored in finish(): no branch around the loads
+    return View{Rows<T, NARROW>(x, ldx), Rows<T, NARROW>(dy, lddy), Rows<float, NARROW>(has_cs() ? chan_scale : mean, has_cs() ? C : 0),
+                Rows<float, NARROW>(has_ca() ? chan_add : mean, has_ca() ? C : 0), Vec1<NARROW>(has_is() ? img_scale : mean)};
+  }
+  // ok false: a row outside the block's range (see Rows<>); its per-image vectors shadow image 0
+  __device__ __forceinline__ void load_raw(const View& vw, long long row, int c, bool ok, Raw& r) const {
+    r.x = vw.X.load(row, c, ok);
+    r.g = vw.G.load(row, c, ok);
     if (SE) {
-      const long long n = (int)row / rows_per_img;     // rows < 2^31 (checked on the host)
-      // absent vectors read a valid dummy (the mean vector) and are ignored in finish(): no branch around the loads
-      r.cs = ld4((chan_scale != nullptr ? chan_scale + n * C : mean) + c);
-      r.ca = ld4((chan_add != nullptr ? chan_add + n * C : mean) + c);
-      r.is = (img_scale != nullptr ? img_scale : mean)[img_scale != nullptr ? n : 0];
+      const int n = (int)row / rows_per_img;     // rows < 2^31 (checked on the host)
+      if (CS) r.cs = vw.CSV.load(n, c, ok);
+      if (CA) r.ca = vw.CAV.load(n, c, ok);
+      if (IS) r.is = vw.ISV.load(has_is() ? n : 0, ok);
     }
   }
   struct Ctx { float4 m, rs, ga, be; };   // per-channel constants of this thread's quad, loaded once
@@ -424,55 +588,75 @@ struct BnBwdCommon {                       // T: storage type of x and dy (and o
   __device__ __forceinline__ void finish(const Ctx& k, const Raw& r, float4& xin, float4& xhat, float4& g) const {
     xin = r.x;
     float4 v = xin;
-    if (pre_swish) v = make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w));
+    if (pre()) v = own4(make_float4(swish_f(v.x), swish_f(v.y), swish_f(v.z), swish_f(v.w)));
     const float4 m = k.m, rs = k.rs;
     xhat = make_float4((v.x - m.x) * rs.x, (v.y - m.y) * rs.y, (v.z - m.z) * rs.z, (v.w - m.w) * rs.w);
     g = r.g;
     if (SE) {
-      if (img_scale != nullptr) g = f4scale(g, r.is);
-      if (chan_scale != nullptr) g = f4mul(g, r.cs);
-      if (chan_add != nullptr) g = f4add(g, r.ca);
+      if (has_is()) g = own4(f4scale(g, r.is));
+      if (has_cs()) g = own4(f4mul(g, r.cs));
+      if (has_ca()) g = f4add(g, r.ca);
     }
-    if (post_swish) {
+    if (post()) {
       const float4 ga = k.ga, be = k.be;
-      g.x *= swish_grad_f(fmaf(xhat.x, ga.x, be.x));
-      g.y *= swish_grad_f(fmaf(xhat.y, ga.y, be.y));
-      g.z *= swish_grad_f(fmaf(xhat.z, ga.z, be.z));
-      g.w *= swish_grad_f(fmaf(xhat.w, ga.w, be.w));
+      g.x *= bn_swish_grad(fmaf(xhat.x, ga.x, be.x));
+      g.y *= bn_swish_grad(fmaf(xhat.y, ga.y, be.y));
+      g.z *= bn_swish_grad(fmaf(xhat.z, ga.z, be.z));
+      g.w *= bn_swish_grad(fmaf(xhat.w, ga.w, be.w));
+      g = own4(g);
     }
   }
 };
 
-template <bool SE, typename T = float>
+template <int RF, typename T = float>
 struct BnBwdOp {
   static constexpr int NV = 2;
-  BnBwdCommon<SE, T> p;
-  typedef typename BnBwdCommon<SE, T>::Raw Raw;
-  typedef typename BnBwdCommon<SE, T>::Ctx Ctx;
+  static constexpr bool kAccum = true;
+  BnBwdCommon<RF, T> p;
+  typedef typename BnBwdCommon<RF, T>::Raw Raw;
+  typedef typename BnBwdCommon<RF, T>::Ctx Ctx;
+  typedef typename BnBwdCommon<RF, T>::View View;
+  __device__ __forceinline__ View view(int) const { return p.view(); }
   __device__ __forceinline__ Ctx ctx(int c) const { return p.ctx(c); }
-  __device__ __forceinline__ void load(int, long long row, int c, Raw& r) const { p.load_raw(row, c, r); }
+  __device__ __forceinline__ void load(const View& vw, int, long long row, int c, Raw& r) const { p.load_raw(vw, row, c, true, r); }
   __device__ __forceinline__ void eval(const Ctx& k, const Raw& r, float4* o) const {
     float4 xin, xhat, g;
     p.finish(k, r, xin, xhat, g);
     o[0] = g;
     o[1] = f4mul(g, xhat);
   }
+  __device__ __forceinline__ void accum(const Ctx& k, const Raw& r, float4 (&acc)[NV]) const {
+    float4 xin, xhat, g;
+    p.finish(k, r, xin, xhat, g);
+    acc[0] = f4add(acc[0], g);
+    acc[1] = f4fma(g, xhat, acc[1]);
+  }
 };
 
 // two plain batch-norm backward reduce passes of the same shape in one launch: segment (blockIdx.z) = problem
+template <int RF>
 struct BnBwdPairOp {
   static constexpr int NV = 2;
-  BnBwdCommon<false> p[2];
+  static constexpr bool kAccum = true;
+  BnBwdCommon<RF> p[2];
   long long rows;
-  typedef BnBwdCommon<false>::Raw Raw;
-  typedef BnBwdCommon<false>::Ctx Ctx;
+  typedef typename BnBwdCommon<RF>::Raw Raw;
+  typedef typename BnBwdCommon<RF>::Ctx Ctx;
+  typedef typename BnBwdCommon<RF>::View View;
+  __device__ __forceinline__ View view(int seg) const { return p[seg].view(); }
   __device__ __forceinline__ Ctx ctx(int c) const { return p[blockIdx.z].ctx(c); }
-  __device__ __forceinline__ void load(int seg, long long row, int c, Raw& r) const { p[seg].load_raw(row - seg * rows, c, r); }
+  __device__ __forceinline__ void load(const View& vw, int seg, long long row, int c, Raw& r) const { p[seg].load_raw(vw, row - seg * rows, c, true, r); }
   __device__ __forceinline__ void eval(const Ctx& k, const Raw& r, float4* o) const {
     float4 xin, xhat, g;
     p[blockIdx.z].finish(k, r, xin, xhat, g);
     o[0] = g;
     o[1] = f4mul(g, xhat);
+  }
+  __device__ __forceinline__ void accum(const Ctx& k, const Raw& r, float4 (&acc)[NV]) const {
+    float4 xin, xhat, g;
+    p[blockIdx.z].finish(k, r, xin, xhat, g);
+    acc[0] = f4add(acc[0], g);
+    acc[1] = f4fma(g, xhat, acc[1]);
   }
 };
 
@@ -494,11 +678,19 @@ struct BnBwdAlt {
   const float *x, *dy, *mean, *rstd, *gamma, *beta, *part;
   float *dgamma, *dbeta, *dx, *dxsum_part;
 };
-template <bool SE, typename T = float>
-__global__ __launch_bounds__(256, SE ? 2 : 3) void bn_bwd_apply_fused_k(BnBwdCommon<SE, T> p, long long rows, const float* __restrict__ part, int nblk,
+// FORM: a mask of the kB* bits fixed at compile time (its kBRowMask part is BnBwdCommon's RF), or kFormGeneric.
+// (two workgroups per CU where the squeeze-excite vectors ride in every row's loads, three otherwise)
+template <int FORM> constexpr int bwd_apply_wgs() { return (FORM < 0 || (FORM & (kBCs | kBCa)) != 0) ? 2 : 3; }
+template <int FORM, typename T = float>
+__global__ __launch_bounds__(256, bwd_apply_wgs<FORM>()) void bn_bwd_apply_fused_k(BnBwdCommon<bwd_row_form(FORM), T> p, long long rows, const float* __restrict__ part, int nblk,
                                                             double inv_n, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                             T* __restrict__ dx, int lddx, int rows_per_block, SkipOut skip,
                                                             float* __restrict__ dxsum_part, BnBwdAlt alt) {
+  typedef BnBwdCommon<bwd_row_form(FORM), T> P;
+  constexpr bool kGen = FORM < 0, NARROW = !kGen;
+  constexpr bool kSkipA = !kGen && (FORM & kBSkipA) != 0, kSkipW = !kGen && (FORM & kBSkipW) != 0;
+  const bool dxsum = kGen ? dxsum_part != nullptr : (FORM & kBDxsum) != 0;
+  typedef typename Rows<T, NARROW>::Row Row;
   if (blockIdx.z == 1) {   // (uniform; the pair form is float only)
     p.x = reinterpret_cast<const T*>(alt.x); p.dy = reinterpret_cast<const T*>(alt.dy); p.mean = alt.mean; p.rstd = alt.rstd; p.gamma = alt.gamma;
     p.beta = alt.beta;
@@ -511,68 +703,88 @@ __global__ __launch_bounds__(256, SE ? 2 : 3) void bn_bwd_apply_fused_k(BnBwdCom
   const int q = t & 7, rl = t >> 3;
   const bool cok = c0 + q * 4 < p.C;
   const int c = cok ? c0 + q * 4 : 0;
-  long long r1 = (long long)(blockIdx.y + 1) * rows_per_block;
-  if (r1 > rows) r1 = rows;
-  long long r = (long long)blockIdx.y * rows_per_block + rl;
+  Row r1 = (Row)(blockIdx.y + 1) * rows_per_block;
+  if (r1 > (Row)rows) r1 = (Row)rows;
+  Row r = (Row)blockIdx.y * rows_per_block + rl;
   if (!cok) r1 = r;
+  const typename P::View vw = p.view();
+  const Rows<T, NARROW> DX(dx, lddx);
+  const Rows<float, NARROW> SK(kGen ? nullptr : skip.d, skip.ld);   // (the compile-time skip forms; the generic one goes through skip.put)
+  // a row's loads: the tensors and per-image vectors, and (accumulating skip form) the skip gradient's old value -- it used to be
+  // read inside finish(), one more dependent memory round trip behind the fold
+  auto fetch = [&](Row rw, bool ok, typename P::Raw& raw, float4& sk) {
+    p.load_raw(vw, rw, c, ok, raw);
+    if (kSkipA) sk = SK.load(rw, c, ok);
+  };
   // first batch of rows fetched BEFORE the fold of the gradient sums (it does not depend on them): one round trip on small maps
-  typename BnBwdCommon<SE, T>::Raw raw0[kBatch];
+  typename P::Raw raw0[kBatch];
+  float4 sk0[kBatch];
 #pragma unroll
-  for (int u = 0; u < kBatch; ++u) {
-    const long long ru = r + u * kRowLanes;
-    p.load_raw(ru < r1 ? ru : 0, c, raw0[u]);
-  }
-  const typename BnBwdCommon<SE, T>::Ctx kc = p.ctx(c);
+  for (int u = 0; u < kBatch; ++u) fetch(r + u * kRowLanes, r + u * kRowLanes < r1, raw0[u], sk0[u]);
+  const typename P::Ctx kc = p.ctx(c);
   double s, sx;
   fold32<8>(part, nblk, p.C, c0, smd, s, sx);
   if (t < 32) {
     s_c1[t] = (float)(s * inv_n);
     s_c2[t] = (float)(sx * inv_n);
-    const int cc = c0 + t;
-    if (blockIdx.y == 0 && cc < p.C) {
-      dbeta[cc] = (float)s;
-      dgamma[cc] = (float)sx;
-    }
   }
   __syncthreads();
-  if (!cok && dxsum_part == nullptr) return;   // (surplus lanes stay for the column-sum reduction, with an empty row range)
+  // (after the barrier: the other 224 threads do not wait for the first row of blocks to publish the parameter gradients)
+  if (t < 32 && blockIdx.y == 0 && c0 + t < p.C) {
+    dbeta[c0 + t] = (float)s;
+    dgamma[c0 + t] = (float)sx;
+  }
+  if (!cok && !dxsum) return;   // (surplus lanes stay for the column-sum reduction, with an empty row range)
   const float4 a = ld4(s_c1 + q * 4), b = ld4(s_c2 + q * 4), ga = kc.ga, rs = kc.rs;
   float4 dsum = f4zero();   // column sum of this thread's dx rows (bias gradient of a conv -> swish -> BN stack)
-  auto finish = [&](long long rw, const typename BnBwdCommon<SE, T>::Raw& raw) {
+  // ok: the row is inside the block's range (narrow forms run the first batch without a branch, as bn_apply_fused_k does)
+  auto finish = [&](Row rw, bool ok, const typename P::Raw& raw, const float4& sk) {
     float4 xin, xhat, g;
-    skip.put(rw, c, raw.g);
+    if (kGen) {
+      if (ok) skip.put(rw, c, raw.g);
+    } else if (kSkipA) {
+      SK.store(rw, c, f4add(sk, raw.g), ok);
+    } else if (kSkipW) {
+      SK.store(rw, c, raw.g, ok);
+    }
     p.finish(kc, raw, xin, xhat, g);
     float4 d;
-    d.x = ga.x * rs.x * (g.x - a.x - xhat.x * b.x);
-    d.y = ga.y * rs.y * (g.y - a.y - xhat.y * b.y);
-    d.z = ga.z * rs.z * (g.z - a.z - xhat.z * b.z);
-    d.w = ga.w * rs.w * (g.w - a.w - xhat.w * b.w);
-    if (p.pre_swish) {
-      d.x *= swish_grad_f(xin.x);
-      d.y *= swish_grad_f(xin.y);
-      d.z *= swish_grad_f(xin.z);
-      d.w *= swish_grad_f(xin.w);
+    // (g - a - xhat * b with its contraction written out, as bn_swish_grad)
+    d.x = ga.x * rs.x * fmaf(-xhat.x, b.x, g.x - a.x);
+    d.y = ga.y * rs.y * fmaf(-xhat.y, b.y, g.y - a.y);
+    d.z = ga.z * rs.z * fmaf(-xhat.z, b.z, g.z - a.z);
+    d.w = ga.w * rs.w * fmaf(-xhat.w, b.w, g.w - a.w);
+    if (p.pre()) {
+      d.x *= bn_swish_grad(xin.x);
+      d.y *= bn_swish_grad(xin.y);
+      d.z *= bn_swish_grad(xin.z);
+      d.w *= bn_swish_grad(xin.w);
     }
-    dsum = f4add(dsum, d);
-    stq(dx + rw * lddx + c, d);
+    d = own4(d);
+    if (dxsum) dsum = f4add(dsum, ok ? d : f4zero());
+    DX.store(rw, c, d, ok);
   };
 #pragma unroll
-  for (int u = 0; u < kBatch; ++u)
-    if (r + u * kRowLanes < r1) finish(r + u * kRowLanes, raw0[u]);
+  for (int u = 0; u < kBatch; ++u) {
+    const bool ok = r + u * kRowLanes < r1;
+    if (NARROW || ok) finish(r + u * kRowLanes, ok, raw0[u], sk0[u]);
+  }
   r += kBatch * kRowLanes;
   for (; r + (kBatch - 1) * kRowLanes < r1; r += kBatch * kRowLanes) {
-    typename BnBwdCommon<SE, T>::Raw raw[kBatch];
+    typename P::Raw raw[kBatch];
+    float4 sk[kBatch];
 #pragma unroll
-    for (int u = 0; u < kBatch; ++u) p.load_raw(r + u * kRowLanes, c, raw[u]);
+    for (int u = 0; u < kBatch; ++u) fetch(r + u * kRowLanes, true, raw[u], sk[u]);
 #pragma unroll
-    for (int u = 0; u < kBatch; ++u) finish(r + u * kRowLanes, raw[u]);
+    for (int u = 0; u < kBatch; ++u) finish(r + u * kRowLanes, true, raw[u], sk[u]);
   }
   for (; r < r1; r += kRowLanes) {
-    typename BnBwdCommon<SE, T>::Raw raw;
-    p.load_raw(r, c, raw);
-    finish(r, raw);
+    typename P::Raw raw;
+    float4 sk;
+    fetch(r, true, raw, sk);
+    finish(r, true, raw, sk);
   }
-  if (dxsum_part == nullptr) return;   // (uniform)
+  if (!dxsum) return;   // (uniform)
 #pragma unroll
   for (int off = 8; off < 64; off <<= 1) {
     dsum.x += __shfl_xor(dsum.x, off);
@@ -594,14 +806,17 @@ __global__ __launch_bounds__(256, SE ? 2 : 3) void bn_bwd_apply_fused_k(BnBwdCom
 template <typename T = float>   // T: storage type of a and b
 struct SumOp {  // column sum of a (optionally times b)
   static constexpr int NV = 1;
+  static constexpr bool kAccum = false;
   const T* a;
   int lda;
   const T* b;  // nullable
   int ldb;
   struct Raw { float4 a, b; };
   struct Ctx {};
+  struct View {};
+  __device__ __forceinline__ View view(int) const { return View(); }
   __device__ __forceinline__ Ctx ctx(int) const { return Ctx(); }
-  __device__ __forceinline__ void load(int, long long row, int c, Raw& r) const {
+  __device__ __forceinline__ void load(const View&, int, long long row, int c, Raw& r) const {
     r.a = ldq(a + row * lda + c);
     r.b = b != nullptr ? ldq(b + row * ldb + c) : make_float4(1.f, 1.f, 1.f, 1.f);
   }
@@ -617,9 +832,10 @@ struct SumOp {  // column sum of a (optionally times b)
 // and the batch norm's stage-1 sums follow without touching the tensors again:
 //     sum g = sum_n gate[n] v1[n] + chan_add[n] v3[n],   sum g xhat = sum_n gate[n] v2[n] + chan_add[n] v4[n]
 // (mliis_se_mlp_bwd_bn forms them).  Replaces the gate-gradient column sum (+ its finalize) and the batch norm's reduce pass.
-template <typename T = float>   // T: storage type of z1 and da2
+template <typename T, bool NARROW>   // T: storage type of z1 and da2; NARROW: 32-bit offsets (Rows<>)
 struct SeBnOp {
   static constexpr int NV = 5;
+  static constexpr bool kAccum = false;
   const T* x;    // z1: the batch norm's input
   int ldx;
   const T* dy;   // da2
@@ -628,9 +844,11 @@ struct SeBnOp {
   struct Raw { float4 x, g; };
   struct Ctx { float4 m, rs, ga, be; };
   __device__ __forceinline__ Ctx ctx(int c) const { return Ctx{ld4(mean + c), ld4(rstd + c), ld4(gamma + c), ld4(beta + c)}; }
-  __device__ __forceinline__ void load(int, long long row, int c, Raw& r) const {
-    r.x = ldq(x + row * ldx + c);
-    r.g = ldq(dy + row * lddy + c);
+  struct View { Rows<T, NARROW> X, G; };
+  __device__ __forceinline__ View view(int) const { return View{Rows<T, NARROW>(x, ldx), Rows<T, NARROW>(dy, lddy)}; }
+  __device__ __forceinline__ void load(const View& vw, int, long long row, int c, Raw& r) const {
+    r.x = vw.X.load(row, c);
+    r.g = vw.G.load(row, c);
   }
   __device__ __forceinline__ void one(float x, float g, float m, float rs, float ga, float be, float* o) const {
     const float xh = (x - m) * rs;
@@ -657,14 +875,17 @@ struct SeBnOp {
 // sum_rows x[row, c] * (mask[row,c]) * dy[row, j], j = 0,1   (final 1x1 conv, Cout = 2: weight gradient)
 struct Outer2Op {
   static constexpr int NV = 2;
+  static constexpr bool kAccum = false;
   const float* x;
   int ldx;
   const float* mask;  // nullable, same layout as x
   const float* dy;    // [rows, 2]
   struct Raw { float4 x, m; float2 d; };
   struct Ctx {};
+  struct View {};
+  __device__ __forceinline__ View view(int) const { return View(); }
   __device__ __forceinline__ Ctx ctx(int) const { return Ctx(); }
-  __device__ __forceinline__ void load(int, long long row, int c, Raw& r) const {
+  __device__ __forceinline__ void load(const View&, int, long long row, int c, Raw& r) const {
     r.x = ld4(x + row * ldx + c);
     r.m = mask != nullptr ? ld4(mask + row * ldx + c) : make_float4(1.f, 1.f, 1.f, 1.f);
     r.d = *reinterpret_cast<const float2*>(dy + row * 2);
@@ -834,6 +1055,173 @@ static inline int ew_grid(long long total_quads) {
   return (int)b;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Routing: which compile-time form a call takes.  The lists are the flag combinations the training passes issue (passes.py); the
+// routing function and the launcher of a kernel expand the same list, so an instance exists exactly for what is routed to it.
+//   apply:    bn0 / bn1 / stem / decoder post-swish BN (kAPost), bn1 with the squeeze-excite pooling (kAPost | kAPool), bn2 plain /
+//             with the identity skip / with drop-connect and skip (0, kARes, kAIsc | kARes), the decoder's conv -> swish -> BN
+//             (kAPre; the pair launch too) and its residual form (kAPre | kARes); bf16 storage: z1 -> a1 (kAPost [| kAPool])
+//   backward: the decoder (kBPre [| kBDxsum]; the pair launch too), post-swish BNs (kBPost), bn2 (0 | kBSkipW | kBSkipA, with
+//             drop-connect kBIs | kBSkip*), bn1 behind the squeeze-excite backward (kBPost | kBCs | kBCa); bf16 storage: bn0, bn1
+// ---------------------------------------------------------------------------------------------------------------
+#define BN_APPLY_FORMS_F32(X) X(kAPost) X(kAPost | kAPool) X(0) X(kARes) X(kAIsc | kARes) X(kAPre) X(kAPre | kARes)
+#define BN_APPLY_FORMS_BF16(X) X(kAPost) X(kAPost | kAPool)
+#define BN_BWD_FORMS_F32(X)                                                                                                   \
+  X(kBPre) X(kBPre | kBDxsum) X(kBPost) X(0) X(kBSkipW) X(kBSkipA) X(kBIs | kBSkipW) X(kBIs | kBSkipA) X(kBPost | kBCs | kBCa)
+#define BN_BWD_FORMS_BF16(X) X(kBPost) X(kBPost | kBCs | kBCa)
+#define BN_BWD_REDUCE_FORMS_F32(X) X(kBPre) X(kBPost) X(0) X(kBIs) X(kBPost | kBCs | kBCa)
+#define BN_BWD_REDUCE_FORMS_BF16(X) X(kBPost) X(kBPost | kBCs | kBCa)
+#define BN_FORM_IS(f) \
+  if (want == (f)) return (f);
+
+static inline int bn_apply_form(bool bf16, bool pre, bool post, bool isc, bool res, bool pool, bool narrow) {
+  if (!narrow) return kFormGeneric;
+  const int want = (pre ? kAPre : 0) | (post ? kAPost : 0) | (isc ? kAIsc : 0) | (res ? kARes : 0) | (pool ? kAPool : 0);
+  if (bf16) {
+    BN_APPLY_FORMS_BF16(BN_FORM_IS)
+  } else {
+    BN_APPLY_FORMS_F32(BN_FORM_IS)
+  }
+  return kFormGeneric;
+}
+static inline int bn_bwd_row_bits(bool pre, bool post, bool is, bool cs, bool ca) {
+  return (pre ? kBPre : 0) | (post ? kBPost : 0) | (is ? kBIs : 0) | (cs ? kBCs : 0) | (ca ? kBCa : 0);
+}
+static inline int bn_bwd_form(bool bf16, int row_bits, bool skip, bool skip_accumulate, bool dxsum, bool narrow) {
+  if (!narrow) return kFormGeneric;
+  const int want = row_bits | (skip ? (skip_accumulate ? kBSkipA : kBSkipW) : 0) | (dxsum ? kBDxsum : 0);
+  if (bf16) {
+    BN_BWD_FORMS_BF16(BN_FORM_IS)
+  } else {
+    BN_BWD_FORMS_F32(BN_FORM_IS)
+  }
+  return kFormGeneric;
+}
+static inline int bn_bwd_reduce_form(bool bf16, int row_bits, bool narrow) {
+  if (!narrow) return kFormGeneric;
+  const int want = row_bits;
+  if (bf16) {
+    BN_BWD_REDUCE_FORMS_BF16(BN_FORM_IS)
+  } else {
+    BN_BWD_REDUCE_FORMS_F32(BN_FORM_IS)
+  }
+  return kFormGeneric;
+}
+
+// a launch of bn_apply_fused_k, whichever instance takes it
+struct BnApplyCall {
+  const void* x;
+  int ldx;
+  void* y;
+  int ldy;
+  long long rows;
+  int C, rows_per_img;
+  BnFold f;
+  const float *gamma, *beta;
+  int pre_swish, post_swish;
+  const float *img_scale, *res;
+  int ldr, rpb;
+  float* pool_part;
+  int cpi;
+  BnApplyAlt alt;
+  dim3 grid;
+  hipStream_t stream;
+};
+template <typename TX, typename TY, int FORM>
+static void bn_apply_go(const BnApplyCall& a) {
+  hipLaunchKernelGGL((bn_apply_fused_k<TX, TY, FORM>), a.grid, dim3(256), 0, a.stream, reinterpret_cast<const TX*>(a.x), a.ldx,
+                     reinterpret_cast<TY*>(a.y), a.ldy, a.rows, a.C, a.rows_per_img, a.f, a.gamma, a.beta, a.pre_swish, a.post_swish, a.img_scale,
+                     a.res, a.ldr, a.rpb, a.pool_part, a.cpi, a.alt);
+}
+static void bn_apply_launch(int form, bool bf16, const BnApplyCall& a) {
+#define BN_CASE_F32(f) \
+  case (f): return bn_apply_go<float, float, (f)>(a);
+#define BN_CASE_BF16(f) \
+  case (f): return bn_apply_go<bf16s, bf16s, (f)>(a);
+  if (bf16) {
+    switch (form) {
+      BN_APPLY_FORMS_BF16(BN_CASE_BF16)
+      default: return bn_apply_go<bf16s, bf16s, kFormGeneric>(a);
+    }
+  }
+  switch (form) {
+    BN_APPLY_FORMS_F32(BN_CASE_F32)
+    default: return bn_apply_go<float, float, kFormGeneric>(a);
+  }
+#undef BN_CASE_F32
+#undef BN_CASE_BF16
+}
+
+// a launch of the batch-norm backward (reduce pass and apply pass), whichever instances take it
+struct BnBwdCall {
+  const void* x;
+  int ldx;
+  const void* dy;
+  int lddy;
+  int rows_per_img, C;
+  const float *mean, *rstd, *gamma, *beta;
+  int pre_swish, post_swish;
+  const float *img_scale, *chan_scale, *chan_add;
+  long long rows;
+  const float* part;
+  int nblk;
+  float *dgamma, *dbeta;
+  void* dx;
+  int lddx, rpb;
+  SkipOut skip;
+  float* dxsum_part;
+  BnBwdAlt alt;
+  dim3 grid;
+  hipStream_t stream;
+};
+template <int RF, typename T>
+static BnBwdCommon<RF, T> bn_bwd_common(const BnBwdCall& a) {
+  return BnBwdCommon<RF, T>{reinterpret_cast<const T*>(a.x), a.ldx, reinterpret_cast<const T*>(a.dy), a.lddy, a.rows_per_img, a.C, a.mean, a.rstd,
+                            a.gamma, a.beta, a.pre_swish, a.post_swish, a.img_scale, a.chan_scale, a.chan_add};
+}
+template <int FORM, typename T>
+static void bn_bwd_apply_go(const BnBwdCall& a) {
+  hipLaunchKernelGGL((bn_bwd_apply_fused_k<FORM, T>), a.grid, dim3(256), 0, a.stream, bn_bwd_common<bwd_row_form(FORM), T>(a), a.rows, a.part, a.nblk,
+                     1.0 / (double)a.rows, a.dgamma, a.dbeta, reinterpret_cast<T*>(a.dx), a.lddx, a.rpb, a.skip, a.dxsum_part, a.alt);
+}
+static void bn_bwd_apply_launch(int form, bool bf16, const BnBwdCall& a) {
+#define BN_CASE_F32(f) \
+  case (f): return bn_bwd_apply_go<(f), float>(a);
+#define BN_CASE_BF16(f) \
+  case (f): return bn_bwd_apply_go<(f), bf16s>(a);
+  if (bf16) {
+    switch (form) {
+      BN_BWD_FORMS_BF16(BN_CASE_BF16)
+      default: return bn_bwd_apply_go<kFormGeneric, bf16s>(a);
+    }
+  }
+  switch (form) {
+    BN_BWD_FORMS_F32(BN_CASE_F32)
+    default: return bn_bwd_apply_go<kFormGeneric, float>(a);
+  }
+#undef BN_CASE_F32
+#undef BN_CASE_BF16
+}
+// the reduce pass (stage 1) of one problem into ws; *g: its geometry
+static int bn_bwd_reduce_launch(int rform, bool bf16, const BnBwdCall& a, float* ws, size_t ws_floats, ColGeom* g, int target) {
+#define BN_CASE_F32(f) \
+  case (f): return launch_colreduce(BnBwdOp<(f), float>{bn_bwd_common<(f), float>(a)}, a.rows, a.C, 1, ws, ws_floats, a.stream, g, "bn_bwd", target);
+#define BN_CASE_BF16(f) \
+  case (f): return launch_colreduce(BnBwdOp<(f), bf16s>{bn_bwd_common<(f), bf16s>(a)}, a.rows, a.C, 1, ws, ws_floats, a.stream, g, "bn_bwd", target);
+  if (bf16) {
+    switch (rform) {
+      BN_BWD_REDUCE_FORMS_BF16(BN_CASE_BF16)
+      default: return launch_colreduce(BnBwdOp<kFormGeneric, bf16s>{bn_bwd_common<kFormGeneric, bf16s>(a)}, a.rows, a.C, 1, ws, ws_floats, a.stream, g, "bn_bwd", target);
+    }
+  }
+  switch (rform) {
+    BN_BWD_REDUCE_FORMS_F32(BN_CASE_F32)
+    default: return launch_colreduce(BnBwdOp<kFormGeneric, float>{bn_bwd_common<kFormGeneric, float>(a)}, a.rows, a.C, 1, ws, ws_floats, a.stream, g, "bn_bwd", target);
+  }
+#undef BN_CASE_F32
+#undef BN_CASE_BF16
+}
+
 }  // namespace mliis
 
 using namespace mliis;
@@ -854,9 +1242,8 @@ int mliis_bn_stats(const float* x, int ldx, long long rows, int C, int pre_swish
                 "bn_stats: bad shape rows=%lld C=%d ld=%d", rows, C, ldx);
   MLIIS_REQUIRE(aligned16(x) && aligned16(ws), MLIIS_ERR_ALIGN, "bn_stats: pointers must be 16-byte aligned");
   MLIIS_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), MLIIS_ERR_ARG, "bn_stats: moving stats must come as a pair");
-  StatsOp op{x, ldx, pre_swish};
   ColGeom g;
-  int rc = launch_colreduce(op, rows, C, 1, ws, ws_floats, stream, &g, "bn_stats");
+  int rc = stats_route(x, ldx, rows, pre_swish, [&](auto op) { return launch_colreduce(op, rows, C, 1, ws, ws_floats, stream, &g, "bn_stats"); });
   if (rc) return rc;
   double n = (double)rows;
   float factor = unbiased_moving_var ? (float)(n / (n - 1.0)) : 1.0f;
@@ -895,83 +1282,42 @@ int mliis_bn_bwd(const float* x, int ldx, const float* dy, int lddy, float* dx, 
                       lddy >= C && lddx >= C && rows_per_img > 0 && aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(stage1_part) &&
                       aligned16(ws) && (stage1_part == nullptr || stage1_nblk > 0),
                   MLIIS_ERR_ARG, "bn_bwd: bad shape / alignment");
-    int gx_, gy_, rpb_;
-    bn_bwd_grid(rows, C, &gx_, &gy_, &rpb_);
-    const bf16s *xb = reinterpret_cast<const bf16s*>(x), *gb = reinterpret_cast<const bf16s*>(dy);
-    bf16s* db = reinterpret_cast<bf16s*>(dx);
-    const bool se_ = img_scale != nullptr || chan_scale != nullptr || chan_add != nullptr;
-    if (stage1_part == nullptr) {   // no producer left stage 1 (the stride-2 layer that lands on a small map): the reduce pass, on bf16 tensors
-      ColGeom g_;
-      int rc_;
-      if (se_) {
-        BnBwdCommon<true, bf16s> p{xb, ldx, gb, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, img_scale, chan_scale, chan_add};
-        rc_ = launch_colreduce(BnBwdOp<true, bf16s>{p}, rows, C, 1, ws, ws_floats, stream, &g_, "bn_bwd", bn_bwd_target(rows, C));
-      } else {
-        BnBwdCommon<false, bf16s> p{xb, ldx, gb, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, nullptr, nullptr, nullptr};
-        rc_ = launch_colreduce(BnBwdOp<false, bf16s>{p}, rows, C, 1, ws, ws_floats, stream, &g_, "bn_bwd", bn_bwd_target(rows, C));
-      }
-      if (rc_) return rc_;
-      stage1_part = ws;
-      stage1_nblk = g_.nblk;
-    }
-    if (se_) {
-      BnBwdCommon<true, bf16s> p{xb, ldx, gb, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, img_scale, chan_scale, chan_add};
-      hipLaunchKernelGGL((bn_bwd_apply_fused_k<true, bf16s>), dim3(gx_, gy_), dim3(256), 0, stream, p, rows, stage1_part, stage1_nblk,
-                         1.0 / (double)rows, dgamma, dbeta, db, lddx, rpb_, SkipOut{nullptr, 0, 0}, (float*)nullptr, BnBwdAlt{});
-    } else {
-      BnBwdCommon<false, bf16s> p{xb, ldx, gb, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, nullptr, nullptr, nullptr};
-      hipLaunchKernelGGL((bn_bwd_apply_fused_k<false, bf16s>), dim3(gx_, gy_), dim3(256), 0, stream, p, rows, stage1_part, stage1_nblk,
-                         1.0 / (double)rows, dgamma, dbeta, db, lddx, rpb_, SkipOut{nullptr, 0, 0}, (float*)nullptr, BnBwdAlt{});
-    }
-    MLIIS_CHECK_LAUNCH("bn_bwd_apply_fused (bf16)");
-    return MLIIS_OK;
+  } else {
+    MLIIS_REQUIRE(dskip == nullptr || (aligned16(dskip) && (lddskip & 3) == 0 && lddskip >= C && dskip != dx), MLIIS_ERR_ARG,
+                  "bn_bwd: bad skip-gradient output");
+    MLIIS_REQUIRE(aligned16(dgamma) && aligned16(dbeta), MLIIS_ERR_ALIGN, "bn_bwd: dgamma / dbeta must be 16-byte aligned");
+    MLIIS_REQUIRE(rows > 1 && rows < (1LL << 31) && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && (lddy & 3) == 0 && (lddx & 3) == 0 &&
+                      ldx >= C && lddy >= C && lddx >= C && rows_per_img > 0,
+                  MLIIS_ERR_ARG, "bn_bwd: bad shape");
+    MLIIS_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(ws) && aligned16(chan_scale) && aligned16(chan_add) &&
+                      aligned16(mean) && aligned16(rstd) && aligned16(gamma) && aligned16(beta),
+                  MLIIS_ERR_ALIGN, "bn_bwd: pointers must be 16-byte aligned");
   }
-  MLIIS_REQUIRE(dskip == nullptr || (aligned16(dskip) && (lddskip & 3) == 0 && lddskip >= C && dskip != dx), MLIIS_ERR_ARG,
-                "bn_bwd: bad skip-gradient output");
-  MLIIS_REQUIRE(aligned16(dgamma) && aligned16(dbeta), MLIIS_ERR_ALIGN, "bn_bwd: dgamma / dbeta must be 16-byte aligned");
-  MLIIS_REQUIRE(rows > 1 && rows < (1LL << 31) && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && (lddy & 3) == 0 && (lddx & 3) == 0 &&
-                    ldx >= C && lddy >= C && lddx >= C && rows_per_img > 0,
-                MLIIS_ERR_ARG, "bn_bwd: bad shape");
-  MLIIS_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(ws) && aligned16(chan_scale) && aligned16(chan_add) &&
-                    aligned16(mean) && aligned16(rstd) && aligned16(gamma) && aligned16(beta),
-                MLIIS_ERR_ALIGN, "bn_bwd: pointers must be 16-byte aligned");
-  SkipOut skip{dskip, lddskip, dskip_accumulate};
+  const bool bf = act_dtype == MLIIS_DT_BF16;
   int gx, gy, rpb;
   bn_bwd_grid(rows, C, &gx, &gy, &rpb);
   const int target = bn_bwd_target(rows, C);
   MLIIS_REQUIRE(dxsum_part == nullptr || (aligned16(dxsum_part) && (size_t)gy * C <= dxsum_floats), MLIIS_ERR_WORKSPACE,
                 "bn_bwd: column-sum buffer unaligned or too small (%zu floats needed)", (size_t)gy * C);
-  ColGeom g;
-  int rc;
-  if (stage1_part != nullptr) {   // stage 1 ({sum g, sum g * xhat} partials [stage1_nblk][2][C]) came from the producer of dy
-    // (the producer computed its sums with the same g: the drop-connect scale -- mliis_conv2d_bwd_data_bn -- or the squeeze-excite
-    // vectors -- mliis_se_bn_bwd_sums + mliis_se_mlp_bwd_bn -- are part of it)
-    MLIIS_REQUIRE(stage1_nblk > 0 && aligned16(stage1_part), MLIIS_ERR_ARG, "bn_bwd: bad external stage-1 partials");
-    if (img_scale != nullptr || chan_scale != nullptr || chan_add != nullptr) {
-      BnBwdCommon<true> p{x, ldx, dy, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, img_scale, chan_scale, chan_add};
-      hipLaunchKernelGGL(bn_bwd_apply_fused_k<true>, dim3(gx, gy), dim3(256), 0, stream, p, rows, stage1_part, stage1_nblk, 1.0 / (double)rows,
-                         dgamma, dbeta, dx, lddx, rpb, skip, dxsum_part, BnBwdAlt{});
-    } else {
-      BnBwdCommon<false> p{x, ldx, dy, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, nullptr, nullptr, nullptr};
-      hipLaunchKernelGGL(bn_bwd_apply_fused_k<false>, dim3(gx, gy), dim3(256), 0, stream, p, rows, stage1_part, stage1_nblk, 1.0 / (double)rows,
-                         dgamma, dbeta, dx, lddx, rpb, skip, dxsum_part, BnBwdAlt{});
-    }
-    MLIIS_CHECK_LAUNCH("bn_bwd_apply_fused");
-    return MLIIS_OK;
-  }
-  if (img_scale != nullptr || chan_scale != nullptr || chan_add != nullptr) {
-    BnBwdCommon<true> p{x, ldx, dy, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, img_scale, chan_scale, chan_add};
-    rc = launch_colreduce(BnBwdOp<true>{p}, rows, C, 1, ws, ws_floats, stream, &g, "bn_bwd", target);
+  // stage 1 ({sum g, sum g * xhat} partials [stage1_nblk][2][C]) may have come from the producer of dy
+  // (the producer computed its sums with the same g: the drop-connect scale -- mliis_conv2d_bwd_data_bn -- or the squeeze-excite
+  // vectors -- mliis_se_bn_bwd_sums + mliis_se_mlp_bwd_bn -- are part of it)
+  MLIIS_REQUIRE(stage1_part == nullptr || (stage1_nblk > 0 && aligned16(stage1_part)), MLIIS_ERR_ARG, "bn_bwd: bad external stage-1 partials");
+  const size_t es = bf ? sizeof(bf16s) : sizeof(float);
+  const bool narrow = narrow_extent(rows, ldx, es) && narrow_extent(rows, lddy, es) && narrow_extent(rows, lddx, es) &&
+                      (dskip == nullptr || narrow_extent(rows, lddskip, sizeof(float)));
+  const int row_bits = bn_bwd_row_bits(pre_swish != 0, post_swish != 0, img_scale != nullptr, chan_scale != nullptr, chan_add != nullptr);
+  BnBwdCall call{x, ldx, dy, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, img_scale, chan_scale, chan_add, rows,
+                 stage1_part, stage1_nblk, dgamma, dbeta, dx, lddx, rpb, SkipOut{dskip, lddskip, dskip_accumulate}, dxsum_part, BnBwdAlt{},
+                 dim3(gx, gy), stream};
+  if (stage1_part == nullptr) {   // no producer left stage 1: the reduce pass
+    ColGeom g;
+    const int rc = bn_bwd_reduce_launch(bn_bwd_reduce_form(bf, row_bits, narrow), bf, call, ws, ws_floats, &g, target);
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_apply_fused_k<true>, dim3(gx, gy), dim3(256), 0, stream, p, rows, ws, g.nblk, 1.0 / (double)rows, dgamma, dbeta,
-                       dx, lddx, rpb, skip, dxsum_part, BnBwdAlt{});
-  } else {
-    BnBwdCommon<false> p{x, ldx, dy, lddy, rows_per_img, C, mean, rstd, gamma, beta, pre_swish, post_swish, nullptr, nullptr, nullptr};
-    rc = launch_colreduce(BnBwdOp<false>{p}, rows, C, 1, ws, ws_floats, stream, &g, "bn_bwd", target);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_apply_fused_k<false>, dim3(gx, gy), dim3(256), 0, stream, p, rows, ws, g.nblk, 1.0 / (double)rows, dgamma, dbeta,
-                       dx, lddx, rpb, skip, dxsum_part, BnBwdAlt{});
+    call.part = ws;
+    call.nblk = g.nblk;
   }
+  bn_bwd_apply_launch(bn_bwd_form(bf, row_bits, dskip != nullptr, dskip_accumulate != 0, dxsum_part != nullptr, narrow), bf, call);
   MLIIS_CHECK_LAUNCH("bn_bwd_apply_fused");
   return MLIIS_OK;
 }
@@ -990,13 +1336,14 @@ int mliis_se_bn_bwd_sums(const float* x, int ldx, const float* dy, int lddy, int
   ColGeom g;
   // (about two workgroups per CU: the squeeze-excite backward folds an image's chunks itself)
   int rc;
-  if (act_dtype == MLIIS_DT_BF16) {
-    SeBnOp<bf16s> op{reinterpret_cast<const bf16s*>(x), ldx, reinterpret_cast<const bf16s*>(dy), lddy, mean, rstd, gamma, beta};
-    rc = launch_colreduce(op, rows_per_img, C, N, part, part_floats, stream, &g, "se_bn_bwd_sums", 512);
-  } else {
-    SeBnOp<float> op{x, ldx, dy, lddy, mean, rstd, gamma, beta};
-    rc = launch_colreduce(op, rows_per_img, C, N, part, part_floats, stream, &g, "se_bn_bwd_sums", 512);
-  }
+  const bool bf = act_dtype == MLIIS_DT_BF16;
+  const size_t es = bf ? sizeof(bf16s) : sizeof(float);
+  const long long rows = (long long)N * rows_per_img;
+  const bool narrow = narrow_extent(rows, ldx, es) && narrow_extent(rows, lddy, es);   // (else: the 64-bit loaders)
+  auto go = [&](auto op) { return launch_colreduce(op, rows_per_img, C, N, part, part_floats, stream, &g, "se_bn_bwd_sums", 512); };
+  const bf16s *xb = reinterpret_cast<const bf16s*>(x), *gb = reinterpret_cast<const bf16s*>(dy);
+  if (bf) rc = narrow ? go(SeBnOp<bf16s, true>{xb, ldx, gb, lddy, mean, rstd, gamma, beta}) : go(SeBnOp<bf16s, false>{xb, ldx, gb, lddy, mean, rstd, gamma, beta});
+  else rc = narrow ? go(SeBnOp<float, true>{x, ldx, dy, lddy, mean, rstd, gamma, beta}) : go(SeBnOp<float, false>{x, ldx, dy, lddy, mean, rstd, gamma, beta});
   if (rc) return rc;
   *nblk = g.nblk;
   return MLIIS_OK;
@@ -1015,10 +1362,11 @@ int mliis_bn_stats_partial(const float* x, int ldx, long long rows, int C, int p
   MLIIS_REQUIRE(x && part && nblk_out, MLIIS_ERR_ARG, "bn_stats_partial: null pointer");
   MLIIS_REQUIRE(rows > 1 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && ldx >= C, MLIIS_ERR_ARG, "bn_stats_partial: bad shape");
   MLIIS_REQUIRE(aligned16(x) && aligned16(part), MLIIS_ERR_ALIGN, "bn_stats_partial: pointers must be 16-byte aligned");
-  StatsOp op{x, ldx, pre_swish};
   ColGeom g;
   // (fewer, taller blocks than the other column reductions: every workgroup of the consumer folds ALL these partials)
-  int rc = launch_colreduce(op, rows, C, 1, part, part_floats, stream, &g, "bn_stats_partial", kStatsPartialTarget);
+  int rc = stats_route(x, ldx, rows, pre_swish, [&](auto op) {
+    return launch_colreduce(op, rows, C, 1, part, part_floats, stream, &g, "bn_stats_partial", kStatsPartialTarget);
+  });
   if (rc) return rc;
   *nblk_out = g.nblk;
   return MLIIS_OK;
@@ -1068,22 +1416,12 @@ int mliis_bn_apply_fused(const float* x, int ldx, float* y, int ldy, long long r
                   (size_t)gy * C, pool_floats);
     *pool_chunks = cpi;
   }
-#define BN_APPLY(TX_, TY_, RES_, ISC_)                                                                                                        \
-  hipLaunchKernelGGL((bn_apply_fused_k<TX_, TY_, RES_, ISC_>), dim3(gx, gy), dim3(256), 0, stream, reinterpret_cast<const TX_*>(x), ldx,         \
-                     reinterpret_cast<TY_*>(y), ldy, rows, C, rows_per_img, f, gamma, beta, pre_swish, post_swish, img_scale, res, ldr, rpb,   \
-                     pool_part, cpi, BnApplyAlt{})
-  const bool has_res = res != nullptr, has_isc = img_scale != nullptr;
-  if (act_dtype == MLIIS_DT_BF16) {   // x and y are bf16 tensors (z1 -> a1 of an MBConv block)
-    if (!has_res && !has_isc) BN_APPLY(bf16s, bf16s, false, false);
-    else BN_APPLY(bf16s, bf16s, true, true);
-  } else if (!has_res && !has_isc) {
-    BN_APPLY(float, float, false, false);
-  } else if (has_res && !has_isc) {
-    BN_APPLY(float, float, true, false);
-  } else {
-    BN_APPLY(float, float, true, true);
-  }
-#undef BN_APPLY
+  const bool bf = act_dtype == MLIIS_DT_BF16;   // x and y are bf16 tensors (z1 -> a1 of an MBConv block)
+  const size_t es = bf ? sizeof(bf16s) : sizeof(float);
+  const bool narrow = narrow_extent(rows, ldx, es) && narrow_extent(rows, ldy, es) && (res == nullptr || narrow_extent(rows, ldr, sizeof(float)));
+  const int form = bn_apply_form(bf, pre_swish != 0, post_swish != 0, img_scale != nullptr, res != nullptr, pool_part != nullptr, narrow);
+  bn_apply_launch(form, bf, BnApplyCall{x, ldx, y, ldy, rows, C, rows_per_img, f, gamma, beta, pre_swish, post_swish, img_scale, res, ldr, rpb,
+                                        pool_part, cpi, BnApplyAlt{}, dim3(gx, gy), stream});
   MLIIS_CHECK_LAUNCH("bn_apply_fused");
   return MLIIS_OK;
 }
@@ -1118,8 +1456,10 @@ int mliis_bn_apply_fused_pair(const float* x0, float* y0, const float* part0, in
     rpb = g2.rows_per_block;
   }
   fit_one_round(rows, gx, 2, &gy, &rpb);
-  hipLaunchKernelGGL((bn_apply_fused_k<float, float, false, false>), dim3(gx, gy, 2), dim3(256), 0, stream, x0, ldx, y0, ldy, rows, C, (int)rows, f0, gamma0, beta0, pre_swish,
-                     post_swish, nullptr, nullptr, 0, rpb, nullptr, 0, BnApplyAlt{x1, y1, f1, gamma1, beta1});
+  const bool narrow = narrow_extent(rows, ldx, sizeof(float)) && narrow_extent(rows, ldy, sizeof(float));
+  bn_apply_launch(bn_apply_form(false, pre_swish != 0, post_swish != 0, false, false, false, narrow), false,
+                  BnApplyCall{x0, ldx, y0, ldy, rows, C, (int)rows, f0, gamma0, beta0, pre_swish, post_swish, nullptr, nullptr, 0, rpb, nullptr, 0,
+                              BnApplyAlt{x1, y1, f1, gamma1, beta1}, dim3(gx, gy, 2), stream});
   MLIIS_CHECK_LAUNCH("bn_apply_fused_pair");
   return MLIIS_OK;
 }
@@ -1147,15 +1487,27 @@ int mliis_bn_bwd_pair(const float* x0, const float* dy0, float* dx0, const float
   bn_bwd_grid(rows, C, &gx, &gy, &rpb);
   MLIIS_REQUIRE(dxsum0 == nullptr || (size_t)gy * C <= dxsum_floats, MLIIS_ERR_WORKSPACE, "bn_bwd_pair: column-sum buffers too small (%zu floats each)",
                 (size_t)gy * C);
-  BnBwdCommon<false> p0{x0, ldx, dy0, lddy, (int)rows, C, mean0, rstd0, gamma0, beta0, pre_swish, post_swish, nullptr, nullptr, nullptr};
-  BnBwdCommon<false> p1{x1, ldx, dy1, lddy, (int)rows, C, mean1, rstd1, gamma1, beta1, pre_swish, post_swish, nullptr, nullptr, nullptr};
+  const bool narrow = narrow_extent(rows, ldx, sizeof(float)) && narrow_extent(rows, lddy, sizeof(float)) && narrow_extent(rows, lddx, sizeof(float));
+  const int row_bits = bn_bwd_row_bits(pre_swish != 0, post_swish != 0, false, false, false);
+  BnBwdCall c0{x0, ldx, dy0, lddy, (int)rows, C, mean0, rstd0, gamma0, beta0, pre_swish, post_swish, nullptr, nullptr, nullptr, rows, ws, 0, dgamma0,
+               dbeta0, dx0, lddx, rpb, SkipOut{nullptr, 0, 0}, dxsum0, BnBwdAlt{}, dim3(gx, gy, 2), stream};
+  BnBwdCall c1 = c0;
+  c1.x = x1; c1.dy = dy1; c1.mean = mean1; c1.rstd = rstd1; c1.gamma = gamma1; c1.beta = beta1;
   ColGeom g;
-  int rc = launch_colreduce(BnBwdPairOp{{p0, p1}, rows}, rows, C, 2, ws, ws_floats, stream, &g, "bn_bwd_pair", bn_bwd_target(rows, C));
+  int rc;
+  const int target = bn_bwd_target(rows, C);
+  // (the pair's reduce pass has the decoder's form and the generic one; bn_bwd_reduce_form names any other)
+  if (bn_bwd_reduce_form(false, row_bits, narrow) == kBPre)
+    rc = launch_colreduce(BnBwdPairOp<kBPre>{{bn_bwd_common<kBPre, float>(c0), bn_bwd_common<kBPre, float>(c1)}, rows}, rows, C, 2, ws, ws_floats, stream, &g,
+                          "bn_bwd_pair", target);
+  else
+    rc = launch_colreduce(BnBwdPairOp<kFormGeneric>{{bn_bwd_common<kFormGeneric, float>(c0), bn_bwd_common<kFormGeneric, float>(c1)}, rows}, rows, C, 2, ws,
+                          ws_floats, stream, &g, "bn_bwd_pair", target);
   if (rc) return rc;
   const float* part1 = ws + (size_t)g.nblk * 2 * C;   // part layout [seg][blk][2][C]
-  hipLaunchKernelGGL(bn_bwd_apply_fused_k<false>, dim3(gx, gy, 2), dim3(256), 0, stream, p0, rows, ws, g.nblk, 1.0 / (double)rows, dgamma0, dbeta0,
-                     dx0, lddx, rpb, SkipOut{nullptr, 0, 0}, dxsum0,
-                     BnBwdAlt{x1, dy1, mean1, rstd1, gamma1, beta1, part1, dgamma1, dbeta1, dx1, dxsum1});
+  c0.nblk = g.nblk;
+  c0.alt = BnBwdAlt{x1, dy1, mean1, rstd1, gamma1, beta1, part1, dgamma1, dbeta1, dx1, dxsum1};
+  bn_bwd_apply_launch(bn_bwd_form(false, row_bits, false, false, dxsum0 != nullptr, narrow), false, c0);
   MLIIS_CHECK_LAUNCH("bn_bwd_pair");
   return MLIIS_OK;
 }

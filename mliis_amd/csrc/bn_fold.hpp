@@ -59,8 +59,13 @@ __device__ __forceinline__ void fold_finish(const FoldAcc& f, double* smd /*[2][
   double x = 0.0;
   if (t < 64) {
     const double* col = smd + (t >> 5) * 32 * 32 + (t & 31);
-#pragma unroll 8
-    for (int k = 0; k < 32; ++k) x += col[k * 32];
+    // all 32 reads in flight before the first add (the adds stay one chain, in lane order): the launch's critical path pays one LDS
+    // round trip here instead of one per unrolled group of eight
+    double v[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) v[k] = col[k * 32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) x += v[k];
   }
   s = x;
   ss = __shfl_down(x, 32, 64);   // (threads 32..63 of wave 0 hold the second statistic)
