@@ -156,6 +156,16 @@ LAYERLOG_SIGNATURES = {
     "mliis_layerlog_append": (_i, [_i, _p, _p, _ll, _p, _i, _p, _i, _p, _sz, _p, _i, _p, C.c_uint, _p]),
 }
 
+# libmliis_clip.so (include/mliis_clip.h): the inner loop's gradient clipping, a library of its own as well
+CLIP_LIB_PATH = os.path.join(_HERE, "libmliis_clip.so")
+CLIP_SIGNATURES = {
+    "mliis_clip_last_error": (C.c_char_p, []),
+    "mliis_clip_chunk_quads": (_i, []),
+    "mliis_clip_workspace_bytes": (_sz, [_i, _i]),
+    "mliis_clip_record_words": (_i, []),
+    "mliis_clip_apply": (_i, [_i, _p, _p, _ll, _p, _i, _p, _i, _f, _f, _p, _sz, _p, _i, _p, _p]),
+}
+
 
 class MliisError(RuntimeError):
     pass
@@ -164,7 +174,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib)."""
+        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -210,3 +220,4 @@ score_lib = _Lib(SCORE_LIB_PATH, SCORE_SIGNATURES, "mliis_score_last_error")
 data_lib = _Lib(DATA_LIB_PATH, DATA_SIGNATURES, "mliis_data_last_error")
 steplog_lib = _Lib(STEPLOG_LIB_PATH, STEPLOG_SIGNATURES, "mliis_steplog_last_error")
 layerlog_lib = _Lib(LAYERLOG_LIB_PATH, LAYERLOG_SIGNATURES, "mliis_layerlog_last_error")
+clip_lib = _Lib(CLIP_LIB_PATH, CLIP_SIGNATURES, "mliis_clip_last_error")

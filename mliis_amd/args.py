@@ -15,6 +15,18 @@ SUPPORTED_MODELS = {"efficientlab"}
 SUPPORTED_SEARCH_ALGS = {"GP"}
 
 # (flag, kwargs) in the reference's order
+def _positive_float(v) -> float:
+    """argparse type of a threshold: a finite float above zero."""
+    import math
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise argparse.ArgumentTypeError("{!r} is not a number".format(v)) from None
+    if not (math.isfinite(f) and f > 0):
+        raise argparse.ArgumentTypeError("{!r} is not a finite positive number".format(v))
+    return f
+
+
 _FLAGS = [
     ("--fine-tune-task", dict(type=str, default=None)),
     ("--fine-tuned-checkpoint", dict(type=str, default=None)),
@@ -159,7 +171,34 @@ _EXT = [
     ("--inner-loop-layer-log-interval", dict(type=int, default=100, metavar="N",
                                              help="with --inner-loop-layer-log: read the per-tensor rings and write a line every N "
                                                   "meta-iterations (the checkpoint cadence)")),
+    ("--inner-clip-norm", dict(type=_positive_float, default=None, metavar="C",
+                               help="clip every training step's loss gradient by its global L2 norm, on the device, between the backward "
+                                    "pass and the optimizer launch (csrc/clip.hip: two more launches in the step's graph): every element "
+                                    "times C / ||g|| when ||g|| > C.  Applies wherever a model is adapted: meta-training and its "
+                                    "--concurrent-tasks lanes, evaluation fine-tunes, early stopping, the k-shot curves, the "
+                                    "update-hyperparameter search, --no-hip-graph, both optimizers.  The --l2 / --l1 terms are formed "
+                                    "inside the optimizer launch and stay outside the clip; a gradient with a NaN or inf in it is left "
+                                    "exactly as it was (--on-divergence sees what it sees without the flag).  Not with --inner-clip-ratio")),
+    ("--inner-clip-ratio", dict(type=_positive_float, default=None, metavar="LAMBDA",
+                                help="clip every training step's loss gradient per trainable tensor instead: tensor t times "
+                                     "LAMBDA max(||theta_t||, eps) / ||g_t|| when ||g_t|| exceeds that bound; the same launches, places "
+                                     "and exclusions as --inner-clip-norm.  Not with --inner-clip-norm")),
+    ("--inner-clip-ratio-eps", dict(type=_positive_float, default=1e-3, metavar="EPS",
+                                    help="with --inner-clip-ratio: the floor of ||theta_t||, which lets zero-initialised biases and "
+                                         "batch-norm betas move")),
 ]
+
+
+def grad_clip(a):
+    """The `grad_clip` argument of the Learner from --inner-clip-norm / --inner-clip-ratio / --inner-clip-ratio-eps, None without them."""
+    c, lam = getattr(a, "inner_clip_norm", None), getattr(a, "inner_clip_ratio", None)
+    if c is not None and lam is not None:
+        raise ValueError("--inner-clip-norm and --inner-clip-ratio exclude each other: one clipping mode per run")
+    if c is not None:
+        return ("norm", _positive_float(c))
+    if lam is not None:
+        return ("ratio", _positive_float(lam), _positive_float(getattr(a, "inner_clip_ratio_eps", 1e-3)))
+    return None
 
 
 def argument_parser(extensions: bool = True) -> argparse.ArgumentParser:
@@ -219,6 +258,9 @@ def model_kwargs(a) -> dict:
     log = dict(step_log=capacity_for(steps)) if inner_loop_log(a) else {}
     if inner_loop_layer_log(a):   # (the per-tensor ring is sized like the step log's: the same rows)
         log["layer_log"] = True
+    clip = grad_clip(a)
+    if clip is not None:   # (absent without the flags as well; its ring holds the steps of one task like the step log's)
+        log.update(grad_clip=clip, clip_log=capacity_for(steps))
     return dict(feature_extractor_name=a.feature_extractor_name, image_size=a.image_size, rsd=a.rsd or None,
                 learning_rate=a.learning_rate, optimizer="sgd" if a.sgd else "adam", l2=a.l2, l1=a.l1, darc1=a.darc1,
                 dice=("dice" in a.loss_name), label_smoothing=a.label_smoothing, final_layer_dropout_rate=a.final_layer_dropout_rate,

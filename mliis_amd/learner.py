@@ -29,12 +29,14 @@ import numpy as np
 import torch
 
 from . import ops, spec
+from . import clip as clip_mod
 from . import layerlog
-from ._lib import MliisError, layerlog_lib, lib, score_lib, steplog_lib
+from ._lib import MliisError, clip_lib, layerlog_lib, lib, score_lib, steplog_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
 from .plan import _Plan, layer_names
+from .steplog import MIN_CAPACITY as MIN_LOG_CAPACITY
 from .steplog import decode as decode_step_log
 
 
@@ -45,7 +47,7 @@ class Learner(_Passes):
                  spatial_pyramid_pooling: bool = False, skip_decoding: bool = False, drop_connect: bool = True, seed: int = 0,
                  device="cuda:0", use_graph: bool = True, max_shots: int = 16, matmul_precision: str = "fp32",
                  small_fused: Optional[bool] = None, dw_march: Optional[bool] = None, fuse_bn2: Optional[bool] = None, fuse_head: Optional[bool] = None,
-                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False):
+                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False, grad_clip=None, clip_log: int = 0):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam' (Adam with beta1=0, the reference default)")
         if not torch.cuda.is_available():
@@ -172,6 +174,34 @@ class Learner(_Passes):
             self._layer_ws = ops.layerlog_workspace(self._layer_table)
             self._delta_ws = ops.layerlog_workspace(self._layer_table)
             self._layer_pin = torch.zeros(self.step_log * T * words + 1, dtype=torch.int32).pin_memory()
+        # grad_clip = ("norm", C) | ("ratio", LAMBDA, EPS): two more launches between the backward pass and the optimizer launch
+        # (ops.clip_apply, captured into the step's graph like the rest) bound the LOSS gradient in arena.grad in place -- by its global L2
+        # norm, or per trainable tensor by LAMBDA * max(||theta_t||, EPS) -- in every training step; the L2 / L1 terms, which the optimizer
+        # launch forms itself, stay outside the clip, and a gradient with a non-finite element is left exactly as it was.  One row of R
+        # records (R = 1 / T) per step goes into a ring of clip_log rows (default steplog.MIN_CAPACITY) addressed by a device cursor of
+        # its own; read_clip_log() fetches them.  Fixed at construction; None (the default): nothing is loaded or allocated and the step
+        # issues the launches it issues without the argument.
+        self.grad_clip = clip_mod.parse(grad_clip)
+        self.clip_log = int(clip_log)
+        if self.clip_log < 0 or (self.clip_log and self.grad_clip is None):
+            raise ValueError("clip_log is the ring capacity of grad_clip: a positive number of rows with it, 0 without, got {}".format(clip_log))
+        self._clip_table = self._clip_ws = self._clip_ring = self._clip_cursor = self._clip_pin = None
+        self._clip_seen = 0      # the clip's device cursor at the last read_clip_log() (or skip_clip_log())
+        self._clip_issued = 0    # steps issued since construction: what that cursor reaches once the stream has drained
+        self._clip_fetched = False   # the pinned copy holds what the last read_step_log() fetched with its own copies
+        if self.grad_clip is not None:
+            clip_lib.load()  # (a missing library is an error here, not at the first step)
+            A = self.arena
+            self.clip_log = self.clip_log or MIN_LOG_CAPACITY
+            self._clip_table = ops.clip_table([p.size for p in A.trainable], self.device)
+            if self._clip_table.n != A.n_trainable_padded or \
+                    any(int(q) * 4 != A.t_off[p.name] for q, p in zip(self._clip_table.segs[:, 0].tolist(), A.trainable)):
+                raise MliisError("the clip's table does not follow the arena's layout")
+            R, words = (len(A.trainable) if self.grad_clip[0] == "ratio" else 1), clip_lib.size("mliis_clip_record_words")
+            self._clip_ring = torch.zeros((self.clip_log, R, words), dtype=torch.int32, device=self.device)
+            self._clip_cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._clip_ws = ops.clip_workspace(self._clip_table)
+            self._clip_pin = torch.zeros(self.clip_log * R * words + 1, dtype=torch.int32).pin_memory()
         self.plans: Dict[object, _Plan] = {}   # key: batch size (training plan) or (batch size, "infer") in bf16-storage mode
         self.max_shots = max_shots
         H = image_size
@@ -556,6 +586,10 @@ class Learner(_Passes):
             if self.darc1:
                 ops.darc1(logits, spec.L2_WEIGHT, dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
         self._backward(P, self.shots_x, P.idx, head_fused=head_fused)
+        if self.grad_clip is not None:   # arena.grad is the loss gradient as the backward pass left it; _apply() consumes what this leaves
+            mode, threshold, eps = self.grad_clip
+            ops.clip_apply(self.arena.grad, self.arena.theta, self._clip_table, self._clip_ws, self._clip_cursor, mode, threshold, eps,
+                           out=self._clip_ring)
         self._apply()
         if self.layer_log:   # the same two arenas per tensor, into the row the step log's cursor names (read here, advanced below)
             ops.layerlog_append(self.arena.grad, self.arena.theta, self._layer_table, self._layer_ws, self._log_cursor, out=self._layer_ring)
@@ -632,6 +666,8 @@ class Learner(_Passes):
             P.steps_run += 1
         if self.step_log:
             self._log_issued += 1
+        if self.grad_clip is not None:
+            self._clip_issued += 1
         self.last_loss = P.loss_out
         return P.loss_out
 
@@ -647,7 +683,10 @@ class Learner(_Passes):
         with torch.cuda.stream(self.stream):
             self._log_pin[:n].copy_(self._log_ring.view(-1), non_blocking=True)
             self._log_pin[n:].copy_(self._log_cursor, non_blocking=True)
+            if self.grad_clip is not None:   # the clip's ring rides along: read_clip_log(last_read=True) needs no wait of its own
+                self._queue_clip_fetch()
         self.stream.synchronize()
+        self._clip_fetched = self.grad_clip is not None
         host = self._log_pin.numpy()
         cursor = int(host[n]) & 0xFFFFFFFF
         records, dropped = decode_step_log(host[:n].reshape(self.step_log, -1), cursor, self._log_seen)
@@ -663,6 +702,42 @@ class Learner(_Passes):
         """Forget the records of the steps issued so far without reading them (no synchronisation): the next read_step_log() starts behind
         them."""
         self._log_seen = self._log_issued & 0xFFFFFFFF
+
+    # ------------------------------------------------------------------------------------------- gradient clipping
+    def _queue_clip_fetch(self):
+        """Queue, on the current stream, the copies of the clip's ring and cursor into their pinned buffer."""
+        n = self._clip_ring.numel()
+        self._clip_pin[:n].copy_(self._clip_ring.view(-1), non_blocking=True)
+        self._clip_pin[n:].copy_(self._clip_cursor, non_blocking=True)
+
+    def read_clip_log(self, last_read: bool = False):
+        """(records [steps, R], dropped): the clip's rows (clip.RECORD_DTYPE; R = 1 by global norm, R = T tensors in arena order per
+        tensor) of the training steps taken since the last call (or skip_clip_log()), in step order, and the number of steps whose rows
+        the ring no longer held.  Waits for the learner's stream.  last_read=True (needs a step log): the rows of exactly the steps the
+        LAST read_step_log() returned, from the copy that call fetched beside its own -- nothing is waited for, queued or consumed (the
+        clip's cursor and the step log's count the same steps)."""
+        if self.grad_clip is None:
+            raise MliisError("this Learner was built without gradient clipping (grad_clip=None)")
+        n = self._clip_ring.numel()
+        if last_read:
+            if not self._clip_fetched:
+                raise MliisError("read_clip_log(last_read=True) follows a read_step_log()")
+            host = self._clip_pin.numpy()
+            first, end = self._log_window
+            return clip_mod.decode(host[:n].reshape(tuple(self._clip_ring.shape)), end, first)
+        with torch.cuda.stream(self.stream):
+            self._queue_clip_fetch()
+        self.stream.synchronize()
+        self._clip_fetched = False
+        host = self._clip_pin.numpy()
+        cursor = int(host[n]) & 0xFFFFFFFF
+        records, dropped = clip_mod.decode(host[:n].reshape(tuple(self._clip_ring.shape)), cursor, self._clip_seen)
+        self._clip_seen = cursor
+        return records, dropped
+
+    def skip_clip_log(self):
+        """Forget the clip rows of the steps issued so far without reading them (no synchronisation)."""
+        self._clip_seen = self._clip_issued & 0xFFFFFFFF
 
     # ------------------------------------------------------------------------------------------- per-tensor log
     @property

@@ -7,6 +7,7 @@ There is no eager/PyTorch fallback -- a missing library or a non-device tensor r
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from collections import namedtuple
 from typing import Optional, Tuple
@@ -14,8 +15,9 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import clip as _clip
 from . import layerlog as _layerlog
-from ._lib import MliisError, data_lib, layerlog_lib, lib, score_lib, steplog_lib
+from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, score_lib, steplog_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1423,26 +1425,31 @@ class LayerTable:
         self.nchunks, self.T = int(chunks.shape[0]), int(segs.shape[0])
 
 
-def layerlog_table(sizes, device, chunks=None, segs=None, n=None) -> LayerTable:
-    """The tables of layerlog_append for arenas that pack tensors of `sizes` elements, each padded to 4 floats (layerlog.chunk_table with
-    the library's chunk size), on `device`.  chunks / segs / n: tables built elsewhere instead (sizes is then ignored).  Either way they
-    are validated here, once, on the host (layerlog.validate_table) -- the kernels follow them as addresses."""
-    cq = layerlog_lib.size("mliis_layerlog_chunk_quads")
+def _chunk_tables(what, cq, sizes, device, chunks, segs, n) -> LayerTable:
+    """layerlog_table / clip_table: the tables for chunks of cq quads, built from `sizes` or taken as given, validated on the host and
+    uploaded; `what` names the caller in the errors."""
     if chunks is None and segs is None:
         table = _layerlog.chunk_table(sizes, cq)
     elif chunks is None or segs is None or n is None:
-        raise MliisError("layerlog_table: chunks, segs and n go together")
+        raise MliisError("{}: chunks, segs and n go together".format(what))
     else:
         table = _layerlog.ChunkTable(np.asarray(chunks), np.asarray(segs), int(n))
     try:
         _layerlog.validate_table(table.chunks, table.segs, table.n, cq)
     except ValueError as e:
-        raise MliisError("layerlog_table: {}".format(e)) from None
+        raise MliisError("{}: {}".format(what, e)) from None
     device = torch.device(device)
     if device.type != "cuda":
-        raise MliisError("layerlog_table: mliis_amd ops need device tensors (no CPU path)")
+        raise MliisError("{}: mliis_amd ops need device tensors (no CPU path)".format(what))
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731  (validated: int32 [.., 4] arrays)
     return LayerTable(up(table.chunks), up(table.segs), table.n)
+
+
+def layerlog_table(sizes, device, chunks=None, segs=None, n=None) -> LayerTable:
+    """The tables of layerlog_append for arenas that pack tensors of `sizes` elements, each padded to 4 floats (layerlog.chunk_table with
+    the library's chunk size), on `device`.  chunks / segs / n: tables built elsewhere instead (sizes is then ignored).  Either way they
+    are validated here, once, on the host (layerlog.validate_table) -- the kernels follow them as addresses."""
+    return _chunk_tables("layerlog_table", layerlog_lib.size("mliis_layerlog_chunk_quads"), sizes, device, chunks, segs, n)
 
 
 def layerlog_workspace(table: LayerTable) -> torch.Tensor:
@@ -1498,6 +1505,74 @@ def layerlog_append(x, y, table: LayerTable, ws, cursor=None, out=None, capacity
         "mliis_layerlog_append", _layerlog.MODES[mode], _ptr(x), _ptr(y), table.n, C.c_void_p(table.chunks.data_ptr()), table.nchunks,
         C.c_void_p(table.segs.data_ptr()), table.T, C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(out.data_ptr()), int(out.shape[0]),
         C.c_void_p(cursor.data_ptr()) if cursor is not None else None, int(row_offset), _stream()))
+    return out
+
+
+def clip_table(sizes, device, chunks=None, segs=None, n=None) -> LayerTable:
+    """The tables of clip_apply for arenas that pack tensors of `sizes` elements, each padded to 4 floats: layerlog_table with the clipping
+    library's chunk size (layerlog.chunk_table), validated here, once, on the host (layerlog.validate_table) -- the kernels follow them as
+    addresses.  chunks / segs / n: tables built elsewhere instead (sizes is then ignored)."""
+    return _chunk_tables("clip_table", clip_lib.size("mliis_clip_chunk_quads"), sizes, device, chunks, segs, n)
+
+
+def clip_workspace(table: LayerTable) -> torch.Tensor:
+    """The workspace of one clip (int32 words; the size is the library's: the call's ring row and one partial per chunk).  Its contents
+    never matter before a launch."""
+    return torch.zeros(clip_lib.size("mliis_clip_workspace_bytes", table.nchunks, table.T) // 4, dtype=torch.int32, device=table.chunks.device)
+
+
+def clip_apply(grad, theta, table: LayerTable, ws, cursor, mode, threshold, eps=_clip.DEFAULT_RATIO_EPS, out=None, capacity=None):
+    """Clip the packed gradient arena `grad` IN PLACE and write one row of R records into the ring `out` (device int32 [capacity, R, 8];
+    allocated zeroed when None, `capacity` rows): mode "norm" -- R = 1, every element times s = threshold / ||grad|| when ||grad|| >
+    threshold; mode "ratio" -- R = table.T, every element of tensor t times s_t = ref_t / ||grad_t|| when ||grad_t|| > ref_t = threshold *
+    max(||theta_t||, eps).  Norms over the counted elements in double, the scale rounded once to fp32, one fp32 product per element; a
+    gradient with a non-finite element is left bit for bit as it was (records flagged bypassed).  Per record {g_l2, ref, scale (fp32 bits),
+    nonfinite, flags (uint32; bit 0 clipped, bit 1 bypassed), 0, 0, 0} -- clip.RECORD_DTYPE reads them.  The row is cursor % capacity,
+    cursor a device int32 [1] the first launch reads and advances itself, so the call can be captured into a HIP graph and replayed.
+    theta: the parameter arena (read only; None allowed in mode "norm"); ws: clip_workspace(table).  Two launches on the current stream in
+    both modes.  libmliis_clip.so (include/mliis_clip.h, csrc/clip.hip)."""
+    if not isinstance(table, LayerTable):
+        raise MliisError("clip_apply table: expected ops.clip_table(...), got {}".format(type(table)))
+    if mode not in _clip.MODES:
+        raise MliisError("clip_apply: mode must be one of {}, got {!r}".format(sorted(_clip.MODES), mode))
+    if theta is None and mode != "norm":
+        raise MliisError("clip_apply: mode 'ratio' needs the parameter arena")
+    for name, t, dt in (("grad", grad, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)) + \
+            ((("theta", theta, torch.float32),) if theta is not None else ()):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MliisError("clip_apply {}: mliis_amd ops need device tensors (no CPU path)".format(name))
+        if dt is not None and t.dtype != dt:
+            raise MliisError("clip_apply {}: expected {} tensor, got {}".format(name, dt, t.dtype))
+        if t.device != table.chunks.device:
+            raise MliisError("clip_apply {}: on {}, the table on {}".format(name, t.device, table.chunks.device))
+    _dense(grad, theta, ws, cursor, out)
+    if grad.numel() != table.n or (theta is not None and theta.numel() != table.n):
+        raise MliisError("clip_apply: grad has {} elements, theta {}, the table addresses {}".format(
+            grad.numel(), None if theta is None else theta.numel(), table.n))
+    if cursor.numel() != 1:
+        raise MliisError("clip_apply: cursor is one int32, got {}".format(cursor.numel()))
+    threshold, eps = float(threshold), float(eps)
+    if not (math.isfinite(threshold) and threshold > 0 and math.isfinite(eps) and eps > 0):
+        raise MliisError("clip_apply: threshold = {!r}, eps = {!r} (finite and positive)".format(threshold, eps))
+    need = clip_lib.size("mliis_clip_workspace_bytes", table.nchunks, table.T)
+    if ws.element_size() != 4 or ws.numel() * 4 < need:
+        raise MliisError("clip_apply ws: {} bytes of 32-bit words needed (clip_workspace), got {} x {} bytes".format(
+            need, ws.numel(), ws.element_size()))
+    words, R = clip_lib.size("mliis_clip_record_words"), (table.T if mode == "ratio" else 1)
+    if out is None:
+        if capacity is None or int(capacity) < 1:
+            raise MliisError("clip_apply: capacity = {!r} (a ring of at least one row, or out=)".format(capacity))
+        out = torch.zeros((int(capacity), R, words), dtype=torch.int32, device=grad.device)
+    else:
+        if not torch.is_tensor(out) or not out.is_cuda or out.device != grad.device or out.dtype != torch.int32 or out.dim() != 3 or \
+                out.shape[1] != R or out.shape[2] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
+            raise MliisError("clip_apply out: expected a device int32 ring of shape ({}, {}, {}), got {} {}".format(
+                "capacity" if capacity is None else int(capacity), R, words, tuple(out.shape) if torch.is_tensor(out) else out,
+                out.dtype if torch.is_tensor(out) else type(out)))
+    _timed("clip_apply", {}, lambda: clip_lib.call(
+        "mliis_clip_apply", _clip.MODES[mode], _ptr(grad), _ptr(theta), table.n, C.c_void_p(table.chunks.data_ptr()), table.nchunks,
+        C.c_void_p(table.segs.data_ptr()), table.T, threshold, eps, C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(out.data_ptr()),
+        int(out.shape[0]), C.c_void_p(cursor.data_ptr()), _stream()))
     return out
 
 

@@ -25,6 +25,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import metaseg
+from . import clip as clip_mod
 from . import layerlog, steplog
 from .spec import BN_MOMENTUM
 
@@ -154,6 +155,16 @@ class Gecko:
                                                          for ln in [learner] + list(lanes))):
             raise ValueError("layer_log=True needs step_log=True and a learner (and lanes) built with the per-tensor log "
                              "(Learner(step_log=CAPACITY, layer_log=True))")
+        # clip rows: when the learner (and every lane) was built with gradient clipping (Learner(grad_clip=...)) and the step log is read
+        # here, the clip's ring is read with it -- Learner.read_clip_log(last_read=True) right after every read_step_log(), from the copy
+        # that call fetched, with no wait of its own -- and the meta-iteration's row gains clip.summarize's keys.  Without clipping the
+        # row has exactly the keys it always had; without the step log the clip's ring is never read.
+        clips = [getattr(ln, "grad_clip", None) is not None and callable(getattr(ln, "read_clip_log", None)) for ln in [learner] + list(lanes)]
+        self.clip_log = self.step_log and all(clips)
+        if self.step_log and any(clips) and not all(clips):
+            raise ValueError("the learner and its lanes must all be built with the same grad_clip")
+        if self.clip_log and any(int(getattr(ln, "clip_log", 0)) < int(ln.step_log) for ln in [learner] + list(lanes)):
+            raise ValueError("a clip ring smaller than the step log's (Learner(clip_log=...) < step_log=...) cannot be read with it")
         self.inner_loop_layers_summary = None   # the per-tensor row of the last meta-iteration that built one
         self.inner_loop_layers_sink = None      # callable(row): train_gecko's writer of inner_loop_layers.jsonl
         self.inner_loop_summary = None   # the row of the last meta-iteration
@@ -421,6 +432,7 @@ class Gecko:
         self._log_state = {id(ln): [ln, [], [], 0] for ln in learners}   # learner, its task indices, (records, dropped) chunks, pending
         # per-tensor log: per learner the (rows, dropped) chunks and delta rows read so far, the delta-ring row of each task, rows in use
         self._layer_state = {id(ln): {"layers": [], "deltas": [], "row": {}, "used": 0} for ln in learners} if self.layer_log else {}
+        self._clip_state = {id(ln): [] for ln in learners} if self.clip_log else {}   # per learner the (rows, dropped) chunks read so far
         for ln in learners:
             skip = getattr(ln, "skip_step_log", None)
             if skip is not None:
@@ -449,6 +461,8 @@ class Gecko:
                 ly["deltas"].append(lane.read_layer_deltas(range(ly["used"])))
                 ly["used"] = 0
             st[2].append(lane.read_step_log())
+            if self.clip_log:   # the clip's rows of the same steps, from the copy that read fetched
+                self._clip_state[id(lane)].append(lane.read_clip_log(last_read=True))
             st[3] = 0
         st[1].append(t)
         st[3] += T
@@ -491,12 +505,17 @@ class Gecko:
         every rank: the flag is a collective OR)."""
         import numpy as np
         L, D = self.learner, self.dist
-        tasks = []
+        tasks, clip_tasks = [], []
         for ln, ts, chunks, _ in self._log_state.values():
             chunks = chunks + [ln.read_step_log()]
             records = np.concatenate([c[0] for c in chunks])
             tasks += list(zip(ts, steplog.split_tasks(records, T, len(ts), sum(c[1] for c in chunks))))
+            if self.clip_log:
+                cc = self._clip_state[id(ln)] + [ln.read_clip_log(last_read=True)]
+                clip_tasks += list(zip(ts, layerlog.split_tasks(np.concatenate([c[0] for c in cc]), T, len(ts), sum(c[1] for c in cc))))
         row = steplog.summarize(tasks, self.meta_iter)
+        if self.clip_log:
+            row.update(clip_mod.summarize(clip_tasks))
         bad = row["nonfinite_steps"] > 0
         if self.on_divergence != "off":   # the ranks must take the same branch, or the next all-reduce hangs
             bad = D.any_true(bad, device=getattr(L, "device", None))
