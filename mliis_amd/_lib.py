@@ -166,6 +166,15 @@ CLIP_SIGNATURES = {
     "mliis_clip_apply": (_i, [_i, _p, _p, _ll, _p, _i, _p, _i, _f, _f, _p, _sz, _p, _i, _p, _p]),
 }
 
+# libmliis_sweep.so (include/mliis_sweep.h): the evaluation threshold sweep's probability histograms, a library of its own as well.
+# MLIIS_SWEEP_LIB: path of an alternative build (kernel experiments, tools/bench_sweep.py); the default is the in-tree build
+SWEEP_LIB_PATH = os.environ.get("MLIIS_SWEEP_LIB", os.path.join(_HERE, "libmliis_sweep.so"))
+SWEEP_SIGNATURES = {
+    "mliis_sweep_last_error": (C.c_char_p, []),
+    "mliis_prob_hist_bins": (_i, []),
+    "mliis_prob_histogram": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+}
+
 
 class MliisError(RuntimeError):
     pass
@@ -174,7 +183,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib)."""
+        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib, sweep_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -221,3 +230,4 @@ data_lib = _Lib(DATA_LIB_PATH, DATA_SIGNATURES, "mliis_data_last_error")
 steplog_lib = _Lib(STEPLOG_LIB_PATH, STEPLOG_SIGNATURES, "mliis_steplog_last_error")
 layerlog_lib = _Lib(LAYERLOG_LIB_PATH, LAYERLOG_SIGNATURES, "mliis_layerlog_last_error")
 clip_lib = _Lib(CLIP_LIB_PATH, CLIP_SIGNATURES, "mliis_clip_last_error")
+sweep_lib = _Lib(SWEEP_LIB_PATH, SWEEP_SIGNATURES, "mliis_sweep_last_error")

@@ -186,6 +186,20 @@ _EXT = [
     ("--inner-clip-ratio-eps", dict(type=_positive_float, default=1e-3, metavar="EPS",
                                     help="with --inner-clip-ratio: the floor of ||theta_t||, which lets zero-initialised biases and "
                                          "batch-norm betas move")),
+    ("--threshold-sweep", dict(action="store_true",
+                               help="sweep the decision threshold in the final evaluation pass over the meta-test (or, with "
+                                    "--eval_val_tasks, meta-val) tasks: every test image leaves a 2 x 256 histogram of its foreground "
+                                    "probability by label class on the device (csrc/sweep.hip: 2 KB per image come back in place of the "
+                                    "four counts of --device-metrics), from which the IoU at every threshold k/256, the best threshold and "
+                                    "a reliability table are derived exactly; written to <checkpoint>/meta-<test|val>_threshold_sweep.json.  "
+                                    "Predictions, saved masks, printed lines and meta-test_results.json stay those of a --device-metrics "
+                                    "run at 0.5.  Not applied to the train-task pass, the update-hyperparameter search, the k-shot curves "
+                                    "or meta-training")),
+    ("--threshold-sweep-val", dict(action="store_true",
+                                   help="with --threshold-sweep (implied): after the meta-test pass run the same pass over the --num_val_tasks "
+                                        "validation tasks and add selected_on_val = {threshold, val_iou, test_iou_at_threshold} to the file: "
+                                        "the threshold chosen on tasks the test score never saw.  Needs --num_val_tasks > 0; not with "
+                                        "--eval_val_tasks")),
 ]
 
 
@@ -199,6 +213,18 @@ def grad_clip(a):
     if lam is not None:
         return ("ratio", _positive_float(lam), _positive_float(getattr(a, "inner_clip_ratio_eps", 1e-3)))
     return None
+
+
+def threshold_sweep(a):
+    """(sweep, on_val) from --threshold-sweep / --threshold-sweep-val.  Kept out of evaluate_kwargs like the prediction writer: only the final
+    evaluation pass over the test (or val) tasks is swept."""
+    on_val = bool(getattr(a, "threshold_sweep_val", False))
+    sweep = bool(getattr(a, "threshold_sweep", False)) or on_val
+    if on_val and getattr(a, "num_val_tasks", 0) <= 0:
+        raise ValueError("--threshold-sweep-val selects the threshold on validation tasks: it needs --num_val_tasks > 0")
+    if on_val and getattr(a, "eval_val_tasks", False):
+        raise ValueError("--threshold-sweep-val with --eval_val_tasks would select and report on the same tasks: use --threshold-sweep alone")
+    return sweep, on_val
 
 
 def argument_parser(extensions: bool = True) -> argparse.ArgumentParser:

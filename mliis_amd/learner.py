@@ -31,7 +31,7 @@ import torch
 from . import ops, spec
 from . import clip as clip_mod
 from . import layerlog
-from ._lib import MliisError, clip_lib, layerlog_lib, lib, score_lib, steplog_lib
+from ._lib import MliisError, clip_lib, layerlog_lib, lib, score_lib, steplog_lib, sweep_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
@@ -911,6 +911,42 @@ class Learner(_Passes):
         self.stream.synchronize()
         masks = unpack_mask(P.bits_pin[n0:].numpy(), H, H)
         return (masks, P.counts_pin[n0:].numpy().astype(np.int64)) if counts else masks
+
+    def histogram_resident(self, idx: Sequence[int], training: bool = False, last_only: bool = False, masks: bool = False):
+        """The threshold sweep's view of predict_resident(idx): int64 [n, 2, 256], per image the histogram of its channel-1 probability
+        split by label class (ops.prob_histogram on the decoder-resolution logits of score_resident's forward pass: 2 KB per image come
+        back).  metrics.counts_from_histogram(...)[..., 128, :] are score_resident's rows bit for bit; the other rows are the counts at the
+        other thresholds k/256.  last_only=True: only the last image of the batch ([1,2,256]), as in mask_resident.  masks=True:
+        (hist, bool [n,H,W]) -- mask_resident's masks packed from the same logits, no second forward pass."""
+        idx = [int(i) for i in idx]
+        N = len(idx)
+        if N == 0:
+            raise ValueError("empty batch")
+        lim = self.max_shots + self._aug_valid if self._aug_valid else self.n_shots
+        if min(idx) < 0 or max(idx) >= lim or any(self.n_shots <= i < self.max_shots for i in idx):
+            raise ValueError("image index out of range of the resident task ({} shots)".format(self.n_shots))
+        P = self._plan(N, infer=True)
+        H = self.arch.image_size
+        n0 = N - 1 if last_only else 0
+        with torch.cuda.stream(self.stream):
+            if P.hist is None:
+                bins = sweep_lib.size("mliis_prob_hist_bins")
+                P.hist = torch.zeros((N, 2, bins), dtype=torch.int32, device=self.device)
+                P.hist_pin = torch.zeros((N, 2, bins), dtype=torch.int32).pin_memory()
+            if masks and P.bits is None:   # (mask_resident's buffers: either call allocates both, each call ends synchronised)
+                words = score_lib.size("mliis_mask_pack_words", H, H)
+                P.bits = torch.zeros((N, words), dtype=torch.int64, device=self.device)
+                P.bits_pin = torch.zeros((N, words), dtype=torch.int64).pin_memory()
+            self._upload_idx(P, idx)
+            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            ops.prob_histogram(P.small[n0:], (H, H), self.shots_y, P.idx[n0:], hist=P.hist[n0:])
+            P.hist_pin[n0:].copy_(P.hist[n0:], non_blocking=True)
+            if masks:
+                ops.mask_pack(P.small[n0:], (H, H), bits=P.bits[n0:])
+                P.bits_pin[n0:].copy_(P.bits[n0:], non_blocking=True)
+        self.stream.synchronize()
+        hist = P.hist_pin[n0:].numpy().astype(np.int64)
+        return (hist, unpack_mask(P.bits_pin[n0:].numpy(), H, H)) if masks else hist
 
     def close(self):
         """Destroy the captured HIP graphs (the buffers themselves are torch tensors and go with the object)."""

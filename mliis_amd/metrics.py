@@ -80,3 +80,121 @@ class EarlyStopper:
 
     def best_num_steps(self):
         return self._best_num_steps
+
+
+# ------------------------------------------------------------------------------------------------ the threshold sweep (host numpy only)
+HIST_BINS = 256   # bins per label class of ops.prob_histogram (mliis_prob_hist_bins)
+
+
+def _hist(hist) -> np.ndarray:
+    h = np.asarray(hist)
+    if h.ndim < 2 or h.shape[-2:] != (2, HIST_BINS) or h.dtype.kind not in "iu":
+        raise ValueError("expected integer histograms [..., 2, {}], got {} {}".format(HIST_BINS, h.shape, h.dtype))
+    return h.astype(np.int64)
+
+
+def counts_from_histogram(hist) -> np.ndarray:
+    """int64 [..., 256, 4] from the histograms of ops.prob_histogram (int [..., 2, 256]: label class, bin): row k = {|P_k & L|, |P_k | L|,
+    |P_k|, |L|} with P_k = (p1 > k/256) = (bin >= k) for k = 1..255 -- row 128 is ops.mask_iou_counts' row bit for bit -- and row 0 the
+    "everything predicted" row (bin >= 0).  Exact: integer suffix sums."""
+    h = _hist(hist)
+    tail = np.cumsum(h[..., ::-1], axis=-1)[..., ::-1]        # tail[..., c, k] = pixels of class c in bins >= k
+    inter, pred = tail[..., 1, :], tail[..., 0, :] + tail[..., 1, :]
+    lab = np.broadcast_to(h[..., 1, :].sum(axis=-1)[..., None], inter.shape)
+    return np.stack([inter, pred + lab - inter, pred, lab], axis=-1)
+
+
+def iou_curve(hist, epsilon: float = 1e-7) -> np.ndarray:
+    """float64 [..., 256]: iou_from_counts' expression on every row of counts_from_histogram (entry 128 = the IoU the project reports)."""
+    c = counts_from_histogram(hist)
+    return (c[..., 0] + epsilon) / (c[..., 1] + epsilon)
+
+
+def reliability(hist) -> dict:
+    """The reliability table of histograms pooled over their leading axes: per bin the pixel count, the foreground share (None for an
+    empty bin) and the bin centre (b + 0.5) / 256 taken as its confidence, and the expected calibration error
+    sum_b count_b / total |share_b - centre_b|."""
+    h = _hist(hist).reshape(-1, 2, HIST_BINS).sum(axis=0)
+    count = h[0] + h[1]
+    centre = (np.arange(HIST_BINS) + 0.5) / HIST_BINS
+    total = int(count.sum())
+    filled = count > 0
+    share = np.full(HIST_BINS, np.nan)
+    share[filled] = h[1][filled] / count[filled]
+    ece = float((count[filled] / total * np.abs(share[filled] - centre[filled])).sum()) if total else float("nan")
+    return {"count": [int(c) for c in count], "foreground_share": [float(s) if f else None for s, f in zip(share, filled)],
+            "confidence": [float(c) for c in centre], "pixels": total, "ece": ece}
+
+
+def mean_curve(curves) -> np.ndarray:
+    """float64 [256]: np.nanmean over the rows of curves [n, 256].  Entry 128 is summed as the 1-D array the evaluation loops average, so
+    it is, to the last bit, float(np.nanmean([...])) of the rows' IoUs at 0.5 (the printed means); the other entries are one reduction
+    over the rows, which may differ from that in the last bit once there are eight rows or more (numpy sums a contiguous vector pairwise)."""
+    import warnings
+    c = np.asarray(curves, dtype=np.float64).reshape(-1, HIST_BINS)
+    half = HIST_BINS // 2
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        m = np.nanmean(c, axis=0) if len(c) else np.full(HIST_BINS, np.nan)
+        m[half] = float(np.nanmean(np.ascontiguousarray(c[:, half]))) if len(c) else np.nan
+    return m
+
+
+def best_threshold_index(curve) -> int:
+    """argmax over k = 1..255 of curve [256]; among equal maxima the k nearest 128 (threshold 0.5), of two equally near the smaller."""
+    c = np.asarray(curve, dtype=np.float64)[1:HIST_BINS]
+    c = np.where(np.isnan(c), -np.inf, c)
+    ks = np.flatnonzero(c == c.max()) + 1
+    return int(min(ks, key=lambda k: (abs(int(k) - HIST_BINS // 2), int(k))))
+
+
+def threshold_summary(curves) -> dict:
+    """From IoU curves [n, 256] (iou_curve rows, or means of them): the thresholds k/256 for k = 1..255, their mean curve (mean_curve),
+    the best threshold (best_threshold_index: ties go to the one nearest 0.5) and the mean IoU at 0.5 and at the best."""
+    m = mean_curve(curves)
+    k = best_threshold_index(m)
+    return {"thresholds": [i / HIST_BINS for i in range(1, HIST_BINS)], "mean_iou": [float(v) for v in m[1:]],
+            "iou_at_0.5": float(m[HIST_BINS // 2]), "best_threshold": k / HIST_BINS, "iou_at_best": float(m[k])}
+
+
+class ThresholdSweep:
+    """The sink of Gecko(threshold_sweep=...): called once per evaluated task with (task name, per-image IoU curves [n, 256], per-image
+    histograms [n, 2, 256]); evaluate_gecko announces every evaluation pass with begin_pass().  summary() aggregates as the printed mean
+    does -- per task the mean over its images, per pass the mean over its tasks, then the mean over the passes -- so its "iou_at_0.5" is
+    the float evaluate_gecko returns."""
+
+    def __init__(self):
+        self.passes = []                                               # per pass: [(task name, mean curve of its images)]
+        self.pooled = np.zeros((2, HIST_BINS), dtype=np.int64)         # all pixels seen
+
+    def begin_pass(self, sample_num=None):
+        self.passes.append([])
+
+    def __call__(self, task_name, curves, hists):
+        if not self.passes:
+            self.begin_pass()
+        self.passes[-1].append((task_name, mean_curve(curves)))
+        self.pooled += _hist(hists).reshape(-1, 2, HIST_BINS).sum(axis=0)
+
+    def pass_curves(self) -> np.ndarray:
+        """float64 [passes, 256]: every pass's mean over its tasks."""
+        return np.stack([mean_curve([c for _, c in p]) for p in self.passes if p]) if any(self.passes) else np.zeros((0, HIST_BINS))
+
+    def mean(self) -> np.ndarray:
+        return mean_curve(self.pass_curves())
+
+    def summary(self) -> dict:
+        out = threshold_summary(self.pass_curves())
+        tasks = {}
+        for p in self.passes:
+            for name, c in p:
+                tasks.setdefault(name, []).append(c)
+        out["tasks"] = {}
+        for name, cs in tasks.items():
+            m = mean_curve(cs)
+            k = best_threshold_index(m)
+            out["tasks"][name] = {"best_threshold": k / HIST_BINS, "iou_at_best": float(m[k]), "iou_at_0.5": float(m[HIST_BINS // 2])}
+        rel = reliability(self.pooled)
+        out["ece"] = rel["ece"]
+        out["reliability"] = rel
+        return out

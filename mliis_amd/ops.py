@@ -17,7 +17,7 @@ import torch
 
 from . import clip as _clip
 from . import layerlog as _layerlog
-from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, score_lib, steplog_lib
+from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, score_lib, steplog_lib, sweep_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1335,6 +1335,33 @@ def mask_pack(small, size, labels=None, idx=None, bits=None, counts=None):
                                              N, Hd, Wd, H, W, C.c_void_p(bits.data_ptr()), C.c_void_p(counts.data_ptr()) if counts is not None else None,
                                              _stream()))
     return bits, counts
+
+
+def prob_histogram(small, size, labels, idx=None, hist=None):
+    """hist [N,2,256] int32 on the device: hist[n][c][b] = the pixels of image n whose label class is c (round(label channel 1) != 0 of
+    labels [S,H,W,2] through idx, nullable) and whose channel-1 probability p1 -- resize(small -> size) -> softmax, the value
+    mask_iou_counts thresholds at 0.5 -- falls in bin b = clamp(ceil(256 p1) - 1, 0, 255), i.e. (b/256, (b+1)/256] (p1 == 0 in bin 0).
+    p1 > k/256 <=> b >= k for k = 1..255, so metrics.counts_from_histogram gives mask_iou_counts' four integers at every threshold k/256,
+    at k = 128 bit for bit.  hist is written whole (it need not be cleared; the counts are below 2^31, the words are the library's
+    unsigned ones).  libmliis_sweep.so (include/mliis_sweep.h, csrc/sweep.hip), loaded at the first call."""
+    N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx, hist)
+    H, W = int(size[0]), int(size[1])
+    if small.shape[-1] != 2 or labels.dim() != 4 or tuple(labels.shape[1:]) != (H, W, 2):
+        raise MliisError("prob_histogram: expected small [N,Hd,Wd,2] and labels [S,{},{},2], got {} / {}".format(H, W, tuple(small.shape),
+                                                                                                           tuple(labels.shape)))
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != N):
+        raise MliisError("prob_histogram: idx must hold {} int32 image indices".format(N))
+    if idx is None and labels.shape[0] < N:
+        raise MliisError("prob_histogram: {} label images for {} predictions".format(labels.shape[0], N))
+    bins = sweep_lib.size("mliis_prob_hist_bins")
+    if hist is not None and (hist.dtype != torch.int32 or tuple(hist.shape) != (N, 2, bins) or not hist.is_cuda):
+        raise MliisError("prob_histogram hist: expected a device int32 tensor of shape {}, got {} {}".format((N, 2, bins), tuple(hist.shape),
+                                                                                                        hist.dtype))
+    hist = torch.empty((N, 2, bins), dtype=torch.int32, device=small.device) if hist is None else hist
+    _timed("prob_histogram", {}, lambda: sweep_lib.call("mliis_prob_histogram", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd, H, W,
+                                                        C.c_void_p(hist.data_ptr()), _stream()))
+    return hist
 
 
 def task_expand_u8(images_u8, masks_u8, src_idx, x, y):

@@ -336,6 +336,9 @@ class _Plan:
         self.counts = self.counts_pin = None
         # Learner.mask_resident: the [N,words] bit-packed masks on the device and their pinned host copy (allocated by its first call)
         self.bits = self.bits_pin = None
+        # Learner.histogram_resident: the [N,2,256] probability histograms on the device and their pinned host copy (allocated by its
+        # first call; with masks=True it packs into the buffers above)
+        self.hist = self.hist_pin = None
 
     @property
     def graph(self):

@@ -125,8 +125,17 @@ class Gecko:
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
                  aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None, step_log: bool = False,
-                 on_divergence: str = "off", layer_log: bool = False, layer_log_interval: int = 100):
+                 on_divergence: str = "off", layer_log: bool = False, layer_log_interval: int = 100, threshold_sweep=None):
         self.learner = learner
+        # threshold_sweep: a sink -- callable(task name, per-image IoU curves [n, 256], per-image histograms [n, 2, 256]), e.g.
+        # metrics.ThresholdSweep.  evaluate()'s tasks then score from Learner.histogram_resident: per test image a 2 x 256 histogram of its
+        # foreground probability by label class comes back (ops.prob_histogram) in place of score_resident's four counts, the IoUs are
+        # those of its k = 128 row -- device_metrics' floats -- and the curves over every threshold k/256 go to the sink.  With a
+        # prediction writer the masks are packed from the same logits.  Early stopping and the k-shot curves are not swept.  Opt-in.
+        self.threshold_sweep = threshold_sweep
+        if threshold_sweep is not None and not all(callable(getattr(ln, "histogram_resident", None)) for ln in [learner] + list(lanes)):
+            raise ValueError("threshold_sweep needs a learner (and lanes) with histogram_resident() (the device Learner; the CPU oracle has "
+                             "none)")
         # step_log: the learner and every lane were built with a step log (Learner(step_log=CAPACITY)); after the task loop of a
         # meta-batch and BEFORE its all-reduce their rings are read, the records attributed to tasks by issue order and condensed into
         # one row (steplog.summarize: inner_loop_summary, handed to inner_loop_sink when one is set).  on_divergence: what a non-finite
@@ -667,7 +676,9 @@ class Gecko:
                             idx = [train_idx[i] for i in schedule[j]]
                         self._fine_tune_step(idx, j, lr, self.lr_scheduler, drop_rate, lane)
             for lane, name, images, labels, train_idx, test_idx, _ in group:
-                if self.prediction_writer is not None:
+                if self.threshold_sweep is not None:
+                    class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, name, eval_sample_num, images, lane)))
+                elif self.prediction_writer is not None:
                     class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, name, eval_sample_num, images, lane)))
                 elif self.device_metrics:
                     class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane)))
@@ -730,7 +741,9 @@ class Gecko:
             save_fine_tuned_checkpoint(L.named_numpy(), save_fine_tuned_checkpoints_dir, task_name, eval_sample_num, inner_iter)
         if self.augmenter is not None and not self.device_aug:
             L.load_task(images, labels)   # the augmented batches replaced the resident task
-        if self.prediction_writer is not None:
+        if self.threshold_sweep is not None:
+            class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, task_name, eval_sample_num, images)))
+        elif self.prediction_writer is not None:
             class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, task_name, eval_sample_num, images)))
         elif self.device_metrics:
             class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx)))
@@ -908,6 +921,35 @@ class Gecko:
         else:
             rows = [L.score_resident(list(train_idx) + [t], training=False)[-1] for t in test_idx]
         return [iou_from_counts(r[0], r[1]) for r in rows]
+
+    def _ious_sweeping(self, train_idx, test_idx, task_name, eval_sample_num=None, images=None, L=None) -> List[float]:
+        """threshold_sweep: _device_ious' per-image IoUs from the k = 128 row of the device's histograms, over the same batches (one
+        histogram_resident call in place of each score_resident call), while the sink receives the task's per-image curves and
+        histograms; with a prediction writer each image's mask comes back from the same call and is saved as _ious_saving saves it."""
+        import numpy as np
+        from .metrics import counts_from_histogram, iou_curve, iou_from_counts
+        L = L or self.learner
+        W = self.prediction_writer
+        masks = None
+        if self._transductive:
+            got = L.histogram_resident(list(test_idx), training=False, masks=W is not None)
+            hists, masks = got if W is not None else (got, None)
+        else:
+            hists, masks = [], []
+            for t in test_idx:
+                got = L.histogram_resident(list(train_idx) + [t], training=False, last_only=True, masks=W is not None)
+                h, m = got if W is not None else (got, None)
+                hists.append(h[-1])
+                if W is not None:
+                    masks.append(m[-1])
+        hists = np.asarray(hists, dtype=np.int64).reshape(len(test_idx), 2, -1)
+        self.threshold_sweep(task_name, iou_curve(hists), hists)
+        if W is not None:
+            for j, t in enumerate(test_idx):
+                image = _to_numpy(images[t]) if (W.overlays and images is not None) else None
+                W.save(task_name, eval_sample_num, j, masks[j], image=image)
+        half = hists.shape[-1] // 2
+        return [iou_from_counts(r[0], r[1]) for r in counts_from_histogram(hists)[:, half]]
 
     def _ious_saving(self, train_idx, test_idx, labels, task_name, eval_sample_num, images=None, L=None) -> List[float]:
         """The per-image IoUs of a task's test images -- _device_ious' with device_metrics, _test_predictions + metrics.iou otherwise, over

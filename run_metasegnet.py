@@ -17,6 +17,9 @@ early-stopping harness of the reference + a built-in GP / expected-improvement o
 curves) scores on the device -- four pixel counts per test image come back instead of its prediction mask; the same IoUs bit for bit.
 --save-predictions DIR [--save-prediction-overlays] (or SAVE_PREDICTIONS=1, the reference's switch): the final evaluation passes save
 every test image's predicted mask as DIR/<task>/sample<k>_query<j>_mask.png (with --device-metrics: one bit per pixel comes back).
+--threshold-sweep [--threshold-sweep-val]: the final pass over the test (or val) tasks also reads back, per test image, a 2 x 256 histogram
+of its foreground probability by label class (csrc/sweep.hip) and writes the IoU at every threshold k/256, the best threshold and a
+reliability table to <checkpoint>/meta-<test|val>_threshold_sweep.json; what is predicted, printed and saved stays at 0.5.
 --resident-dataset: the tasks stay on the device as the bytes the dataset stores (4 per pixel, not 20); a task's shots are expanded on
 the device when it becomes resident (csrc/taskload.hip) -- and resampled to --image_size when the shards hold another size
 (--stored-image-size N).
@@ -39,7 +42,7 @@ if ROOT not in sys.path:
 
 from mliis_amd import checkpoint as ckpt  # noqa: E402
 from mliis_amd.args import (argument_parser, augment_mode, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler, model_kwargs,  # noqa: E402
-                            prediction_writer, stored_image_size, train_kwargs)
+                            prediction_writer, stored_image_size, threshold_sweep, train_kwargs)
 
 
 def _dataset(args, device, rank):
@@ -140,9 +143,16 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
     name = "test"
     if args.eval_val_tasks:
         test_set, name = val_set, "val"
+    sweep_on, sweep_on_val = threshold_sweep(args)   # (this pass only: not the train tasks above, the search or the k-shot curves)
+    sweep = None
+    if sweep_on:
+        from mliis_amd.metrics import ThresholdSweep
+        sweep = ThresholdSweep()
+        assert not sweep_on_val or (val_set is not None and len(val_set) > 0), "--threshold-sweep-val: the val set has no tasks"
     print("Evaluating {}-shot learning on meta-{} tasks.".format(args.shots, name))
     mean_test_iou, task_name_iou_map = evaluate_gecko(learner, test_set, lr_scheduler=lr_scheduler, lanes=lanes, prediction_writer=writer,
-                                                      serially_eval_all_tasks=args.serially_eval_all_test_tasks, **ek)
+                                                      serially_eval_all_tasks=args.serially_eval_all_test_tasks,
+                                                      **({"threshold_sweep": sweep} if sweep is not None else {}), **ek)
     print("Evaluated meta-{} tasks:".format(name))
     print(task_name_iou_map)
     if mean_train_iou is not None:
@@ -153,6 +163,32 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
     with open(out, "w") as f:
         json.dump(task_name_iou_map, f)
     print("Wrote results to {}".format(out))
+    if sweep is not None:
+        _write_threshold_sweep(args, name, sweep, learner, lr_scheduler, val_set if sweep_on_val else None, lanes, ek)
+
+
+def _write_threshold_sweep(args, name, sweep, learner, lr_scheduler, val_set, lanes, ek):
+    """--threshold-sweep: <checkpoint>/meta-<test|val>_threshold_sweep.json from the final pass's sink (metrics.ThresholdSweep.summary:
+    "iou_at_0.5" is the printed mean).  --threshold-sweep-val (val_set given): the same pass then runs over the validation tasks -- after the
+    test pass, which has consumed the random state it always does -- and selected_on_val = the threshold that is best there, with the
+    test IoU at it (and the val curve it was read from).  The pass's own prints are dropped: the run's output stays that of a run without the flag."""
+    import contextlib
+    import io
+    from mliis_amd.eval import evaluate_gecko
+    from mliis_amd.metrics import HIST_BINS, ThresholdSweep
+    doc = sweep.summary()
+    if val_set is not None:
+        on_val = ThresholdSweep()
+        with contextlib.redirect_stdout(io.StringIO()):
+            evaluate_gecko(learner, val_set, lr_scheduler=lr_scheduler, lanes=lanes, threshold_sweep=on_val,
+                           serially_eval_all_tasks=args.serially_eval_all_test_tasks, **dict(ek, save_fine_tuned_checkpoints=False))
+        v = on_val.summary()
+        k = int(round(v["best_threshold"] * HIST_BINS))
+        doc["selected_on_val"] = {"threshold": v["best_threshold"], "val_iou": v["iou_at_best"], "test_iou_at_threshold": float(sweep.mean()[k]),
+                                  "val_mean_iou": v["mean_iou"]}
+    out = os.path.join(args.checkpoint, "meta-{}_threshold_sweep.json".format(name))
+    with open(out, "w") as f:
+        json.dump(doc, f)
 
 
 def main(argv=None, learner_factory=None, device=None):
@@ -162,6 +198,7 @@ def main(argv=None, learner_factory=None, device=None):
     print("Experiment started at: {}".format(start))
     args = argument_parser().parse_args(argv)
     stored_image_size(args)   # (a stored size other than --image_size without --resident-dataset is refused before anything is built)
+    threshold_sweep(args)     # (... and so is a --threshold-sweep-val without validation tasks or with --eval_val_tasks)
     random.seed(args.seed)
     aug_pool = None
     if args.augment and args.augment_on_host and args.augment_workers != 0:   # forked workers: created before anything initialises the GPU
