@@ -13,6 +13,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from .steplog import decode_ring
+
 RECORD_WORDS = 8
 RECORD_DTYPE = np.dtype([("g_l2", "<f4"), ("ref", "<f4"), ("scale", "<f4"), ("nonfinite", "<u4"), ("flags", "<u4"), ("zero", "<u4", (3,))])
 assert RECORD_DTYPE.itemsize == 4 * RECORD_WORDS
@@ -41,17 +43,9 @@ def parse(grad_clip) -> Optional[Tuple[str, float, float]]:
 
 def decode(ring, cursor: int, last_cursor: int = 0) -> Tuple[np.ndarray, int]:
     """(records [steps, R], dropped): the rows written between the counter values last_cursor and cursor, oldest first, and how many of
-    them the ring no longer holds -- steplog.decode for a ring of [capacity, R, 8] words (the counters are taken modulo 2^32 like the
+    them the ring no longer holds -- steplog.decode_ring for a ring of [capacity, R, 8] words (the counters are taken modulo 2^32 like the
     device's)."""
-    words = np.ascontiguousarray(np.asarray(ring)).view(np.uint32)
-    if words.ndim != 3 or words.shape[2] != RECORD_WORDS or words.shape[0] < 1 or words.shape[1] < 1:
-        raise ValueError("expected a [capacity, R, {}] ring, got {}".format(RECORD_WORDS, words.shape))
-    capacity, R = words.shape[:2]
-    new = (int(cursor) - int(last_cursor)) & 0xFFFFFFFF
-    kept = min(new, capacity)
-    pos = (int(cursor) - kept + np.arange(kept, dtype=np.int64)) & 0xFFFFFFFF
-    records = words[pos % capacity].copy().view(RECORD_DTYPE).reshape(kept, R)
-    return records, new - kept
+    return decode_ring(ring, cursor, last_cursor, RECORD_DTYPE, "R")
 
 
 def clipped_steps(records: np.ndarray) -> np.ndarray:

@@ -5,22 +5,14 @@
 // launch advances, so the launches replay inside the step's captured graph.
 #include <float.h>
 #include <math.h>
-#include <stdarg.h>
 
 #include "../../include/mliis_clip.h"
-#include "common.hpp"
+#include "arena_reduce.hpp"
 
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_clip_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_clip_err, sizeof(g_clip_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_clip_err)
 
 // One workgroup of kClipThreads threads per chunk in both launches: thread t handles quads t, t + 256, ... of the chunk (consecutive lanes,
 // consecutive 16 bytes), so what a thread sums and in which order depends on the chunk table alone.  A chunk is at most kClipChunkQuads
@@ -45,8 +37,6 @@ struct Sum {
   double gss, tss;
   unsigned long long nf;
 };
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // element `idx` of the chunk (idx < valid: inside the tensor's count, not its padding)
 __device__ __forceinline__ void grad_elem(float v, unsigned idx, unsigned valid, double& ss, unsigned& nf) {
@@ -124,28 +114,8 @@ __global__ __launch_bounds__(kClipThreads) void clip_partial_k(const float* __re
 
   double gss = 0.0, tss = 0.0;
   unsigned nf = 0u;   // (a thread sees at most 64 elements of a chunk)
-  // kClipDepth quads of each arena are requested before the first of them is used (layerlog_partial_k's loop); the order in which a thread
-  // consumes its elements -- and with it every sum -- is the order of the plain loop
-  int i = tid;
-  for (; i + (kClipDepth - 1) * kClipThreads < quads; i += kClipDepth * kClipThreads) {
-    float4 a[kClipDepth], b[kClipDepth];
-#pragma unroll
-    for (int u = 0; u < kClipDepth; ++u) a[u] = ld4(g + (i + u * kClipThreads) * 4);
-    if (MODE == MLIIS_CLIP_RATIO) {
-#pragma unroll
-      for (int u = 0; u < kClipDepth; ++u) b[u] = ld4(w + (i + u * kClipThreads) * 4);
-    } else {
-#pragma unroll
-      for (int u = 0; u < kClipDepth; ++u) b[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < kClipDepth; ++u) sum_quad<MODE>(a[u], b[u], (unsigned)(i + u * kClipThreads) * 4u, valid, gss, tss, nf);
-  }
-  for (; i < quads; i += kClipThreads) {
-    const float4 a = ld4(g + i * 4);
-    const float4 b = MODE == MLIIS_CLIP_RATIO ? ld4(w + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sum_quad<MODE>(a, b, (unsigned)i * 4u, valid, gss, tss, nf);
-  }
+  stream_quads<kClipDepth, MODE == MLIIS_CLIP_RATIO ? 2 : 1, kClipThreads>(
+      g, w, tid, quads, [&](int i, float4 a, float4 b) { sum_quad<MODE>(a, b, (unsigned)i * 4u, valid, gss, tss, nf); });
 
   Sum s;
   s.gss = gss;
@@ -177,8 +147,6 @@ __device__ __forceinline__ Sum fold_partials(const ClipPartial* __restrict__ par
   }
   return block_fold(s, s_wave);
 }
-
-__device__ __forceinline__ unsigned sat_u32(unsigned long long v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; }
 
 // one fp32 multiplication per element (__fmul_rn is never contracted into a fused multiply-add)
 __device__ __forceinline__ float4 scaled(float4 v, float s) {
@@ -250,19 +218,11 @@ int mliis_clip_apply(int mode, float* g, const float* theta, long long n, const 
                      hipStream_t stream) {
   MLIIS_REQUIRE(mode == MLIIS_CLIP_NORM || mode == MLIIS_CLIP_RATIO, MLIIS_ERR_ARG, "clip_apply: mode = %d (0 norm, 1 ratio)", mode);
   MLIIS_REQUIRE(g && chunks && segs && ws && ring && cursor && (theta || mode == MLIIS_CLIP_NORM), MLIIS_ERR_ARG, "clip_apply: null pointer");
-  MLIIS_REQUIRE(n > 0 && (n & 3) == 0, MLIIS_ERR_ARG, "clip_apply: n must be a positive multiple of 4 (arena is padded)");
-  MLIIS_REQUIRE(n / 4 <= 0x7fffffffll, MLIIS_ERR_ARG, "clip_apply: n = %lld (the tables address quads with 32 bits)", n);
-  MLIIS_REQUIRE(T >= 1, MLIIS_ERR_ARG, "clip_apply: T = %d (at least one tensor)", T);
-  MLIIS_REQUIRE(nchunks >= T && (long long)nchunks <= n / 4, MLIIS_ERR_ARG,
-                "clip_apply: nchunks = %d (every one of the %d tensors has a chunk, every chunk a quad of the %lld)", nchunks, T, n / 4);
-  MLIIS_REQUIRE(capacity >= 1, MLIIS_ERR_ARG, "clip_apply: capacity = %d (the ring holds at least one row)", capacity);
+  if (int e = check_chunk_sizes("clip_apply", n, nchunks, T, capacity)) return e;
   MLIIS_REQUIRE(isfinite(threshold) && threshold > 0.f, MLIIS_ERR_ARG, "clip_apply: threshold = %g (finite and positive)", (double)threshold);
   MLIIS_REQUIRE(mode == MLIIS_CLIP_NORM || (isfinite(eps) && eps > 0.f), MLIIS_ERR_ARG, "clip_apply: eps = %g (finite and positive)", (double)eps);
-  MLIIS_REQUIRE(ws_bytes >= mliis_clip_workspace_bytes(nchunks, T), MLIIS_ERR_ARG, "clip_apply: workspace of %zu bytes, %zu needed", ws_bytes,
-                mliis_clip_workspace_bytes(nchunks, T));
-  MLIIS_REQUIRE(aligned16(g) && aligned16(theta) && aligned16(chunks) && aligned16(segs) && aligned16(ws) && aligned16(ring), MLIIS_ERR_ALIGN,
-                "clip_apply: g, theta, chunks, segs, ws and ring must be 16-byte aligned");
-  MLIIS_REQUIRE((reinterpret_cast<uintptr_t>(cursor) & 3u) == 0, MLIIS_ERR_ALIGN, "clip_apply: cursor must be 4-byte aligned");
+  if (int e = check_chunk_buffers("clip_apply", "g, theta", g, theta, chunks, segs, ws, ws_bytes, mliis_clip_workspace_bytes(nchunks, T), ring, cursor))
+    return e;
   const int4* ch = reinterpret_cast<const int4*>(chunks);
   const int4* sg = reinterpret_cast<const int4*>(segs);
   unsigned char* w = reinterpret_cast<unsigned char*>(ws);

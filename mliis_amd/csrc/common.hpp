@@ -1,6 +1,7 @@
 // Shared device/host helpers for libmliis_hip (gfx950 / CDNA4 only; wave = 64).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,6 +11,18 @@
 namespace mliis {
 
 int set_error(int code, const char* fmt, ...);
+
+// A library's own error slot, defined once per library inside namespace mliis: the thread-local buffer `var` its *_last_error() returns,
+// and the set_error that MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH of everything linked into that library report through.
+#define MLIIS_DEFINE_ERROR_SLOT(var)              \
+  static thread_local char var[512] = "";         \
+  int set_error(int code, const char* fmt, ...) { \
+    va_list ap;                                   \
+    va_start(ap, fmt);                            \
+    vsnprintf(var, sizeof(var), fmt, ap);         \
+    va_end(ap);                                   \
+    return code;                                  \
+  }
 
 #define MLIIS_REQUIRE(cond, code, ...)                 \
   do {                                                 \

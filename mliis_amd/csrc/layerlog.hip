@@ -2,22 +2,13 @@
 // libmliis_score.so, libmliis_data.so and libmliis_steplog.so -- the training step's library, the step log's and their C ABIs are untouched
 // by it.  Two launches at the tail of a step reduce the packed gradient and parameter arenas per tensor and write one record per tensor
 // into the ring row the step log's device cursor names; the cursor is only read here, so the launches replay inside the step's graph.
-#include <stdarg.h>
-
 #include "../../include/mliis_layerlog.h"
-#include "common.hpp"
+#include "arena_reduce.hpp"
 
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_layerlog_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_layerlog_err, sizeof(g_layerlog_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_layerlog_err)
 
 // One workgroup of kLayerThreads threads per chunk: thread t reads quads t, t + 256, ... of the chunk from both arenas (consecutive lanes
 // read consecutive 16 bytes), so what a thread sums and in which order depends on the chunk table alone.  A chunk is at most
@@ -38,8 +29,6 @@ struct LayerPartial {   // one chunk, 48 bytes
   Stat x, y;
 };
 static_assert(sizeof(Stat) == 24 && sizeof(LayerPartial) == 48, "partial layout");
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __device__ __forceinline__ Stat stat_zero() {
   Stat s;
@@ -118,28 +107,11 @@ __global__ __launch_bounds__(kLayerThreads) void layerlog_partial_k(const float*
   const unsigned limit = base + (unsigned)ch.w;
 
   Stat sx = stat_zero(), sy = stat_zero();
-  // kLayerDepth quads of each arena are requested before the first of them is used (steplog_append_k's loop); the order in which a thread
-  // consumes its elements -- and with it every sum -- is the order of the plain loop
-  int i = tid;
-  for (; i + (kLayerDepth - 1) * kLayerThreads < quads; i += kLayerDepth * kLayerThreads) {
-    float4 a[kLayerDepth], b[kLayerDepth];
-#pragma unroll
-    for (int u = 0; u < kLayerDepth; ++u) a[u] = ld4(x + (i + u * kLayerThreads) * 4);
-#pragma unroll
-    for (int u = 0; u < kLayerDepth; ++u) b[u] = ld4(y + (i + u * kLayerThreads) * 4);
-#pragma unroll
-    for (int u = 0; u < kLayerDepth; ++u) {
-      const unsigned idx = base + (unsigned)(i + u * kLayerThreads) * 4u;
-      stat_quad(x_of<MODE>(a[u], b[u]), idx, limit, sx);
-      stat_quad(b[u], idx, limit, sy);
-    }
-  }
-  for (; i < quads; i += kLayerThreads) {
-    const float4 a = ld4(x + i * 4), b = ld4(y + i * 4);
+  stream_quads<kLayerDepth, 2, kLayerThreads>(x, y, tid, quads, [&](int i, float4 a, float4 b) {
     const unsigned idx = base + (unsigned)i * 4u;
     stat_quad(x_of<MODE>(a, b), idx, limit, sx);
     stat_quad(b, idx, limit, sy);
-  }
+  });
 
   // workgroup fold: a fixed butterfly inside each wave, then the waves in index order
 #pragma unroll
@@ -162,8 +134,6 @@ __global__ __launch_bounds__(kLayerThreads) void layerlog_partial_k(const float*
     part[blockIdx.x] = p;
   }
 }
-
-__device__ __forceinline__ unsigned sat_u32(unsigned long long v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; }
 
 // ---- launch 2: one tensor per wave folds its chunks' partials in chunk order and writes its record
 __global__ __launch_bounds__(kLayerThreads) void layerlog_fold_k(const LayerPartial* __restrict__ part, const int4* __restrict__ segs, int T,
@@ -218,17 +188,9 @@ int mliis_layerlog_append(int mode, const float* x, const float* y, long long n,
                           hipStream_t stream) {
   MLIIS_REQUIRE(x && y && chunks && segs && ws && ring, MLIIS_ERR_ARG, "layerlog_append: null pointer");
   MLIIS_REQUIRE(mode == MLIIS_LAYERLOG_STEP || mode == MLIIS_LAYERLOG_DELTA, MLIIS_ERR_ARG, "layerlog_append: mode = %d (0 step, 1 delta)", mode);
-  MLIIS_REQUIRE(n > 0 && (n & 3) == 0, MLIIS_ERR_ARG, "layerlog_append: n must be a positive multiple of 4 (arena is padded)");
-  MLIIS_REQUIRE(n / 4 <= 0x7fffffffll, MLIIS_ERR_ARG, "layerlog_append: n = %lld (the tables address quads with 32 bits)", n);
-  MLIIS_REQUIRE(T >= 1, MLIIS_ERR_ARG, "layerlog_append: T = %d (at least one tensor)", T);
-  MLIIS_REQUIRE(nchunks >= T && (long long)nchunks <= n / 4, MLIIS_ERR_ARG,
-                "layerlog_append: nchunks = %d (every one of the %d tensors has a chunk, every chunk a quad of the %lld)", nchunks, T, n / 4);
-  MLIIS_REQUIRE(capacity >= 1, MLIIS_ERR_ARG, "layerlog_append: capacity = %d (the ring holds at least one row)", capacity);
-  MLIIS_REQUIRE(ws_bytes >= mliis_layerlog_workspace_bytes(nchunks), MLIIS_ERR_ARG, "layerlog_append: workspace of %zu bytes, %zu needed",
-                ws_bytes, mliis_layerlog_workspace_bytes(nchunks));
-  MLIIS_REQUIRE(aligned16(x) && aligned16(y) && aligned16(chunks) && aligned16(segs) && aligned16(ws) && aligned16(ring), MLIIS_ERR_ALIGN,
-                "layerlog_append: x, y, chunks, segs, ws and ring must be 16-byte aligned");
-  MLIIS_REQUIRE((reinterpret_cast<uintptr_t>(cursor) & 3u) == 0, MLIIS_ERR_ALIGN, "layerlog_append: cursor must be 4-byte aligned");
+  if (int e = check_chunk_sizes("layerlog_append", n, nchunks, T, capacity)) return e;
+  if (int e = check_chunk_buffers("layerlog_append", "x, y", x, y, chunks, segs, ws, ws_bytes, mliis_layerlog_workspace_bytes(nchunks), ring, cursor))
+    return e;
   const int4* ch = reinterpret_cast<const int4*>(chunks);
   const int4* sg = reinterpret_cast<const int4*>(segs);
   LayerPartial* part = reinterpret_cast<LayerPartial*>(ws);

@@ -4,22 +4,13 @@
 // capture of an inner step).
 // Reference: GradientDescentOptimizer apply under UPDATE_OPS (models/efficientlab.py:301,315-317; args.py:151-152),
 // L2 = 5e-4 * sum ||w||^2 / 2 over non-BN trainables (models/regularizers.py:4-10) folded in as grad += 5e-4 * w.
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.hpp"
 
 namespace mliis {
 
-static thread_local char g_err[512] = "";
-
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_err)
 
 __device__ __forceinline__ float sign_f(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }   // tf.abs' gradient: sign(0) = 0
 // gradient of the weight regularisers of models/regularizers.py:4-19 on the masked (non batch-norm) quads: l2 * w + l1 * sign(w)

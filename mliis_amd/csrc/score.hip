@@ -2,8 +2,6 @@
 // the training step's library and its C ABI (include/mliis_hip.h) are untouched by it -- that shares the per-pixel arithmetic of the
 // decoder tail with head.hip through head_math.hpp.
 // Reference: meta_learners/supervised_reptile/supervised_reptile/reptile.py:526-549 (_iou) behind models/efficientlab.py:166-176.
-#include <stdarg.h>
-
 #include "../../include/mliis_score.h"
 #include "common.hpp"
 #include "head_math.hpp"
@@ -11,14 +9,7 @@
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_score_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_score_err, sizeof(g_score_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_score_err)
 
 // Scoring an evaluation image needs two integers, not a mask: counts[n] = {|P & L|, |P | L|, |P|, |L|} with P the channel-1 prediction
 // (the resize of `small` to the image, softmax, p1 > 0.5f -- bilinear_sample / softmax2, the arithmetic of resize_fwd_k<2> followed by

@@ -2,22 +2,13 @@
 // and libmliis_data.so -- the training step's library and its C ABI (include/mliis_hip.h) are untouched by it.  One launch at the tail of a
 // step reduces the packed gradient and parameter arenas and appends one record to a ring in device memory; the ring position is a device
 // counter, so the launch replays inside the step's captured graph.
-#include <stdarg.h>
-
 #include "../../include/mliis_steplog.h"
-#include "common.hpp"
+#include "arena_reduce.hpp"
 
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_steplog_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_steplog_err, sizeof(g_steplog_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_steplog_err)
 
 // The grid is a constant: kLogBlocks workgroups of kLogThreads threads, thread t of the grid reads quads t, t + 65536, t + 2 * 65536, ...
 // of both arenas (consecutive lanes read consecutive 16 bytes), so what a thread sums and in which order depends on n alone.
@@ -35,8 +26,6 @@ struct LogPartial {   // one workgroup's share, 32 bytes
 constexpr size_t kLogPartialsAt = 16;
 constexpr size_t kLogWorkspaceBytes = kLogPartialsAt + (size_t)kLogBlocks * sizeof(LogPartial);
 
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 __device__ __forceinline__ void grad_elem(float v, double& ss, float& amax, unsigned& nf) {
   if (finite_f(v)) {
     const double d = (double)v;   // (squared in double: 1e30^2 is past fp32)
@@ -51,8 +40,6 @@ __device__ __forceinline__ unsigned nonfinite4(float4 w) {
   return (finite_f(w.x) ? 0u : 1u) + (finite_f(w.y) ? 0u : 1u) + (finite_f(w.z) ? 0u : 1u) + (finite_f(w.w) ? 0u : 1u);
 }
 
-__device__ __forceinline__ unsigned sat_u32(unsigned long long v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; }
-
 __global__ __launch_bounds__(kLogThreads) void steplog_append_k(const unsigned* __restrict__ loss4, const unsigned* __restrict__ lr_dev,
                                                                 const float* __restrict__ grad, const float* __restrict__ theta,
                                                                 long long nquads, unsigned* __restrict__ ticket, LogPartial* __restrict__ part,
@@ -62,40 +49,19 @@ __global__ __launch_bounds__(kLogThreads) void steplog_append_k(const unsigned* 
   __shared__ unsigned long long s_gnf[kLogThreads], s_tnf[kLogThreads];
   __shared__ int s_last;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const long long stride = (long long)kLogBlocks * kLogThreads;
   const long long first = (long long)blockIdx.x * kLogThreads + tid;
 
   double ss = 0.0;
   float amax = 0.f;
   unsigned gnf = 0u, tnf = 0u;   // (a thread sees n / 65536 elements: 32 bits hold them for any n the arenas can have)
-  // The launch has one wave per SIMD, so a thread that waits for each 16-byte load before it asks for the next one is bound by memory
-  // latency: kLogDepth quads of each arena are requested before the first of them is used.  The order in which a thread consumes its
-  // elements -- and with it every sum -- is the order of the plain loop.
-  long long i = first;
-  for (; i + (kLogDepth - 1) * stride < nquads; i += kLogDepth * stride) {
-    float4 g[kLogDepth], w[kLogDepth];
-#pragma unroll
-    for (int u = 0; u < kLogDepth; ++u) g[u] = ld4(grad + (i + u * stride) * 4);
-#pragma unroll
-    for (int u = 0; u < kLogDepth; ++u) w[u] = ld4(theta + (i + u * stride) * 4);
-#pragma unroll
-    for (int u = 0; u < kLogDepth; ++u) {
-      grad_elem(g[u].x, ss, amax, gnf);
-      grad_elem(g[u].y, ss, amax, gnf);
-      grad_elem(g[u].z, ss, amax, gnf);
-      grad_elem(g[u].w, ss, amax, gnf);
-    }
-#pragma unroll
-    for (int u = 0; u < kLogDepth; ++u) tnf += nonfinite4(w[u]);
-  }
-  for (; i < nquads; i += stride) {
-    const float4 g = ld4(grad + i * 4), w = ld4(theta + i * 4);
+  // (the launch has one wave per SIMD: kLogDepth quads of each arena in flight, consumed in the order of the plain loop)
+  stream_quads<kLogDepth, 2, kLogBlocks * kLogThreads>(grad, theta, first, nquads, [&](long long, float4 g, float4 w) {
     grad_elem(g.x, ss, amax, gnf);
     grad_elem(g.y, ss, amax, gnf);
     grad_elem(g.z, ss, amax, gnf);
     grad_elem(g.w, ss, amax, gnf);
     tnf += nonfinite4(w);
-  }
+  });
 
   // workgroup fold: a fixed butterfly inside each wave, then the waves in index order
   unsigned long long gn = gnf, tn = tnf;

@@ -1,8 +1,6 @@
 // libmliis_sweep.so: the evaluation threshold sweep -- per-image histograms of the foreground probability (include/mliis_sweep.h).  A
 // library of its own beside libmliis_hip.so and libmliis_score.so, neither of which (nor their headers) is touched by it; it shares the
 // per-pixel arithmetic of the decoder tail with head.hip and score.hip through head_math.hpp.
-#include <stdarg.h>
-
 #include "../../include/mliis_sweep.h"
 #include "common.hpp"
 #include "head_math.hpp"
@@ -10,14 +8,7 @@
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_sweep_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_sweep_err, sizeof(g_sweep_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_sweep_err)
 
 constexpr int kBins = 256;      // bins per label class (mliis_prob_hist_bins)
 constexpr int kStrip = 4096;    // image pixels per workgroup: 16 per thread

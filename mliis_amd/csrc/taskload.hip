@@ -2,22 +2,13 @@
 // libmliis_hip.so and libmliis_score.so -- the training step's library and its C ABI (include/mliis_hip.h) are untouched by it.
 // Reference: data/input_fn.py:28-65 (image -> float32 0..255, mask -> (255 - m, m) / 255); the resampling the reference's docstring
 // promises and its code does not have (it reshapes) is stated in the header.
-#include <stdarg.h>
-
 #include "../../include/mliis_data.h"
 #include "common.hpp"
 
 namespace mliis {
 
 // (this library's own error slot: common.hpp's MLIIS_REQUIRE / MLIIS_CHECK_LAUNCH report through set_error of the library they are linked into)
-static thread_local char g_data_err[512] = "";
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_data_err, sizeof(g_data_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+MLIIS_DEFINE_ERROR_SLOT(g_data_err)
 
 // k / 255 correctly rounded in fp32 for the 256 byte values: evaluated by the compiler (IEEE round to nearest), so the label values do
 // not depend on how the device divides.  numpy's float32 division gives the same 256 floats (tests/test_taskload_cpu.py).

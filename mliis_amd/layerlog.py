@@ -14,7 +14,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .steplog import _json_number, nonfinite_steps
+from .steplog import _json_number, decode_ring, nonfinite_steps
 
 RECORD_WORDS = 8
 # step mode: x = the gradient, y = the parameters; delta mode: x = a - b, y = b
@@ -100,16 +100,8 @@ def validate_table(chunks, segs, n: int, chunk_quads: int) -> None:
 
 def decode(ring, cursor: int, last_cursor: int = 0) -> Tuple[np.ndarray, int]:
     """(records [steps, T], dropped): the rows written between the counter values last_cursor and cursor, oldest first, and how many the
-    ring no longer holds -- steplog.decode for a ring of [capacity, T, 8] words (the counters are the step log's)."""
-    words = np.ascontiguousarray(np.asarray(ring)).view(np.uint32)
-    if words.ndim != 3 or words.shape[2] != RECORD_WORDS or words.shape[0] < 1 or words.shape[1] < 1:
-        raise ValueError("expected a [capacity, T, {}] ring, got {}".format(RECORD_WORDS, words.shape))
-    capacity, T = words.shape[:2]
-    new = (int(cursor) - int(last_cursor)) & 0xFFFFFFFF
-    kept = min(new, capacity)
-    pos = (int(cursor) - kept + np.arange(kept, dtype=np.int64)) & 0xFFFFFFFF
-    records = words[pos % capacity].copy().view(RECORD_DTYPE).reshape(kept, T)
-    return records, new - kept
+    ring no longer holds -- steplog.decode_ring for a ring of [capacity, T, 8] words (the counters are the step log's)."""
+    return decode_ring(ring, cursor, last_cursor, RECORD_DTYPE, "T")
 
 
 def split_tasks(records: np.ndarray, steps_per_task: int, n_tasks: int, dropped: int = 0) -> List[np.ndarray]:

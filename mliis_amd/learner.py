@@ -40,6 +40,13 @@ from .steplog import MIN_CAPACITY as MIN_LOG_CAPACITY
 from .steplog import decode as decode_step_log
 
 
+def _queue_ring_fetch(pin, ring, cursor):
+    """Queue, on the current stream, the copies of a device ring and of its cursor into the pinned buffer `pin` (ring.numel() + 1 words)."""
+    n = ring.numel()
+    pin[:n].copy_(ring.view(-1), non_blocking=True)
+    pin[n:].copy_(cursor, non_blocking=True)
+
+
 class Learner(_Passes):
     def __init__(self, feature_extractor_name: str = "efficientnet-b0", image_size: int = 224, rsd: Optional[Sequence[int]] = (2, 4),
                  learning_rate: float = 1e-3, optimizer: str = "sgd", l2: bool = False, l1: bool = False, darc1: bool = False,
@@ -681,10 +688,9 @@ class Learner(_Passes):
             raise MliisError("this Learner was built without a step log (step_log=0)")
         n = self._log_ring.numel()
         with torch.cuda.stream(self.stream):
-            self._log_pin[:n].copy_(self._log_ring.view(-1), non_blocking=True)
-            self._log_pin[n:].copy_(self._log_cursor, non_blocking=True)
+            _queue_ring_fetch(self._log_pin, self._log_ring, self._log_cursor)
             if self.grad_clip is not None:   # the clip's ring rides along: read_clip_log(last_read=True) needs no wait of its own
-                self._queue_clip_fetch()
+                _queue_ring_fetch(self._clip_pin, self._clip_ring, self._clip_cursor)
         self.stream.synchronize()
         self._clip_fetched = self.grad_clip is not None
         host = self._log_pin.numpy()
@@ -704,12 +710,6 @@ class Learner(_Passes):
         self._log_seen = self._log_issued & 0xFFFFFFFF
 
     # ------------------------------------------------------------------------------------------- gradient clipping
-    def _queue_clip_fetch(self):
-        """Queue, on the current stream, the copies of the clip's ring and cursor into their pinned buffer."""
-        n = self._clip_ring.numel()
-        self._clip_pin[:n].copy_(self._clip_ring.view(-1), non_blocking=True)
-        self._clip_pin[n:].copy_(self._clip_cursor, non_blocking=True)
-
     def read_clip_log(self, last_read: bool = False):
         """(records [steps, R], dropped): the clip's rows (clip.RECORD_DTYPE; R = 1 by global norm, R = T tensors in arena order per
         tensor) of the training steps taken since the last call (or skip_clip_log()), in step order, and the number of steps whose rows
@@ -726,7 +726,7 @@ class Learner(_Passes):
             first, end = self._log_window
             return clip_mod.decode(host[:n].reshape(tuple(self._clip_ring.shape)), end, first)
         with torch.cuda.stream(self.stream):
-            self._queue_clip_fetch()
+            _queue_ring_fetch(self._clip_pin, self._clip_ring, self._clip_cursor)
         self.stream.synchronize()
         self._clip_fetched = False
         host = self._clip_pin.numpy()
@@ -749,8 +749,7 @@ class Learner(_Passes):
         """(host words [rows, T, 8], device cursor) after the learner's stream has drained; ring and cursor through pinned memory."""
         n = ring.numel()
         with torch.cuda.stream(self.stream):
-            self._layer_pin[:n].copy_(ring.view(-1), non_blocking=True)
-            self._layer_pin[n:].copy_(self._log_cursor, non_blocking=True)
+            _queue_ring_fetch(self._layer_pin, ring, self._log_cursor)
         self.stream.synchronize()
         host = self._layer_pin.numpy()
         return host[:n].reshape(tuple(ring.shape)), int(host[n]) & 0xFFFFFFFF

@@ -1401,6 +1401,39 @@ def steplog_workspace(device) -> torch.Tensor:
     return torch.zeros(steplog_lib.size("mliis_steplog_workspace_bytes") // 4, dtype=torch.int32, device=device)
 
 
+def _log_tensors(what, tensors, device, device_of):
+    """steplog_append / layerlog_append / clip_apply: every (name, tensor, dtype | None) is a device tensor of that dtype on `device`,
+    which the errors call `device_of`."""
+    for name, t, dt in tensors:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MliisError("{} {}: mliis_amd ops need device tensors (no CPU path)".format(what, name))
+        if dt is not None and t.dtype != dt:
+            raise MliisError("{} {}: expected {} tensor, got {}".format(what, name, dt, t.dtype))
+        if t.device != device:
+            raise MliisError("{} {}: on {}, {} on {}".format(what, name, t.device, device_of, device))
+
+
+def _log_workspace(what, ws, need):
+    """The same three: ws holds `need` bytes of 32-bit words (the NAME_workspace() of what = NAME_...)."""
+    if ws.element_size() != 4 or ws.numel() * 4 < need:
+        raise MliisError("{} ws: {} bytes of 32-bit words needed ({}_workspace), got {} x {} bytes".format(
+            what, need, what.split("_")[0], ws.numel(), ws.element_size()))
+
+
+def _log_ring(what, out, capacity, tail, device):
+    """The same three: the ring, a zeroed device int32 [capacity, *tail] when out is None, else `out` checked to be one of that shape."""
+    if out is None:
+        if capacity is None or int(capacity) < 1:
+            raise MliisError("{}: capacity = {!r} (a ring of at least one {}, or out=)".format(what, capacity, "record" if len(tail) == 1 else "row"))
+        return torch.zeros((int(capacity),) + tail, dtype=torch.int32, device=device)
+    if not torch.is_tensor(out) or not out.is_cuda or out.device != device or out.dtype != torch.int32 or tuple(out.shape[1:]) != tail or \
+            out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
+        raise MliisError("{} out: expected a device int32 ring of shape ({}), got {} {}".format(
+            what, ", ".join(str(v) for v in ("capacity" if capacity is None else int(capacity),) + tail),
+            tuple(out.shape) if torch.is_tensor(out) else out, out.dtype if torch.is_tensor(out) else type(out)))
+    return out
+
+
 def steplog_append(loss4, lr_dev, grad, theta, ws, cursor, out=None, capacity=None):
     """Append one record of a training step to the ring `out` (device int32 [capacity, 8]; allocated zeroed when None, `capacity` rows):
     words {loss, ce, iou (loss4[0..2], bit for bit), lr (*lr_dev), grad_l2, grad_absmax (over the finite elements of grad; fp32 bits),
@@ -1408,35 +1441,16 @@ def steplog_append(loss4, lr_dev, grad, theta, ws, cursor, out=None, capacity=No
     device int32 [1] the launch reads and advances itself, so the call can be captured into a HIP graph and replayed.  grad / theta: the
     packed fp32 arenas (same length, a multiple of 4, read only); ws: steplog_workspace().  One launch on the current stream.
     libmliis_steplog.so (include/mliis_steplog.h, csrc/steplog.hip)."""
-    for name, t, dt in (("loss4", loss4, torch.float32), ("lr_dev", lr_dev, torch.float32), ("grad", grad, torch.float32),
-                        ("theta", theta, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise MliisError("steplog_append {}: mliis_amd ops need device tensors (no CPU path)".format(name))
-        if dt is not None and t.dtype != dt:
-            raise MliisError("steplog_append {}: expected {} tensor, got {}".format(name, dt, t.dtype))
-        if t.device != grad.device:
-            raise MliisError("steplog_append {}: on {}, grad on {}".format(name, t.device, grad.device))
+    _log_tensors("steplog_append", (("loss4", loss4, torch.float32), ("lr_dev", lr_dev, torch.float32), ("grad", grad, torch.float32),
+                                    ("theta", theta, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)), grad.device, "grad")
     _dense(loss4, lr_dev, grad, theta, ws, cursor, out)
     if loss4.numel() < 3 or lr_dev.numel() < 1 or cursor.numel() != 1:
         raise MliisError("steplog_append: loss4 holds at least 3 floats, lr_dev one float and cursor one int32 (got {} / {} / {})".format(
             loss4.numel(), lr_dev.numel(), cursor.numel()))
     if grad.numel() != theta.numel():
         raise MliisError("steplog_append: grad has {} elements, theta {}".format(grad.numel(), theta.numel()))
-    need = steplog_lib.size("mliis_steplog_workspace_bytes")
-    if ws.element_size() != 4 or ws.numel() * 4 < need:
-        raise MliisError("steplog_append ws: {} bytes of 32-bit words needed (steplog_workspace), got {} x {} bytes".format(need, ws.numel(),
-                                                                                                                      ws.element_size()))
-    words = steplog_lib.size("mliis_steplog_record_words")
-    if out is None:
-        if capacity is None or int(capacity) < 1:
-            raise MliisError("steplog_append: capacity = {!r} (a ring of at least one record, or out=)".format(capacity))
-        out = torch.zeros((int(capacity), words), dtype=torch.int32, device=grad.device)
-    else:
-        if not torch.is_tensor(out) or not out.is_cuda or out.device != grad.device or out.dtype != torch.int32 or out.dim() != 2 or \
-                out.shape[1] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
-            raise MliisError("steplog_append out: expected a device int32 ring of shape ({}, {}), got {} {}".format(
-                "capacity" if capacity is None else int(capacity), words, tuple(out.shape) if torch.is_tensor(out) else out,
-                out.dtype if torch.is_tensor(out) else type(out)))
+    _log_workspace("steplog_append", ws, steplog_lib.size("mliis_steplog_workspace_bytes"))
+    out = _log_ring("steplog_append", out, capacity, (steplog_lib.size("mliis_steplog_record_words"),), grad.device)
     _timed("steplog_append", {}, lambda: steplog_lib.call("mliis_steplog_append", _ptr(loss4), _ptr(lr_dev), _ptr(grad), _ptr(theta),
                                                           grad.numel(), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()),
                                                           int(out.shape[0]), C.c_void_p(cursor.data_ptr()), _stream()))
@@ -1498,14 +1512,8 @@ def layerlog_append(x, y, table: LayerTable, ws, cursor=None, out=None, capacity
         raise MliisError("layerlog_append table: expected ops.layerlog_table(...), got {}".format(type(table)))
     if mode not in _layerlog.MODES:
         raise MliisError("layerlog_append: mode must be one of {}, got {!r}".format(sorted(_layerlog.MODES), mode))
-    for name, t, dt in (("x", x, torch.float32), ("y", y, torch.float32), ("ws", ws, None)) + \
-            ((("cursor", cursor, torch.int32),) if cursor is not None else ()):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise MliisError("layerlog_append {}: mliis_amd ops need device tensors (no CPU path)".format(name))
-        if dt is not None and t.dtype != dt:
-            raise MliisError("layerlog_append {}: expected {} tensor, got {}".format(name, dt, t.dtype))
-        if t.device != table.chunks.device:
-            raise MliisError("layerlog_append {}: on {}, the table on {}".format(name, t.device, table.chunks.device))
+    _log_tensors("layerlog_append", (("x", x, torch.float32), ("y", y, torch.float32), ("ws", ws, None)) +
+                 ((("cursor", cursor, torch.int32),) if cursor is not None else ()), table.chunks.device, "the table")
     _dense(x, y, ws, cursor, out)
     if x.numel() != table.n or y.numel() != table.n:
         raise MliisError("layerlog_append: x has {} elements, y {}, the table addresses {}".format(x.numel(), y.numel(), table.n))
@@ -1513,21 +1521,8 @@ def layerlog_append(x, y, table: LayerTable, ws, cursor=None, out=None, capacity
         raise MliisError("layerlog_append: cursor is one int32, got {}".format(cursor.numel()))
     if int(row_offset) < 0 or int(row_offset) > 0xFFFFFFFF:
         raise MliisError("layerlog_append: row_offset = {!r} (an unsigned 32-bit number)".format(row_offset))
-    need = layerlog_lib.size("mliis_layerlog_workspace_bytes", table.nchunks)
-    if ws.element_size() != 4 or ws.numel() * 4 < need:
-        raise MliisError("layerlog_append ws: {} bytes of 32-bit words needed (layerlog_workspace), got {} x {} bytes".format(
-            need, ws.numel(), ws.element_size()))
-    words = layerlog_lib.size("mliis_layerlog_record_words")
-    if out is None:
-        if capacity is None or int(capacity) < 1:
-            raise MliisError("layerlog_append: capacity = {!r} (a ring of at least one row, or out=)".format(capacity))
-        out = torch.zeros((int(capacity), table.T, words), dtype=torch.int32, device=x.device)
-    else:
-        if not torch.is_tensor(out) or not out.is_cuda or out.device != x.device or out.dtype != torch.int32 or out.dim() != 3 or \
-                out.shape[1] != table.T or out.shape[2] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
-            raise MliisError("layerlog_append out: expected a device int32 ring of shape ({}, {}, {}), got {} {}".format(
-                "capacity" if capacity is None else int(capacity), table.T, words, tuple(out.shape) if torch.is_tensor(out) else out,
-                out.dtype if torch.is_tensor(out) else type(out)))
+    _log_workspace("layerlog_append", ws, layerlog_lib.size("mliis_layerlog_workspace_bytes", table.nchunks))
+    out = _log_ring("layerlog_append", out, capacity, (table.T, layerlog_lib.size("mliis_layerlog_record_words")), x.device)
     _timed("layerlog_append", {}, lambda: layerlog_lib.call(
         "mliis_layerlog_append", _layerlog.MODES[mode], _ptr(x), _ptr(y), table.n, C.c_void_p(table.chunks.data_ptr()), table.nchunks,
         C.c_void_p(table.segs.data_ptr()), table.T, C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(out.data_ptr()), int(out.shape[0]),
@@ -1564,14 +1559,8 @@ def clip_apply(grad, theta, table: LayerTable, ws, cursor, mode, threshold, eps=
         raise MliisError("clip_apply: mode must be one of {}, got {!r}".format(sorted(_clip.MODES), mode))
     if theta is None and mode != "norm":
         raise MliisError("clip_apply: mode 'ratio' needs the parameter arena")
-    for name, t, dt in (("grad", grad, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)) + \
-            ((("theta", theta, torch.float32),) if theta is not None else ()):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise MliisError("clip_apply {}: mliis_amd ops need device tensors (no CPU path)".format(name))
-        if dt is not None and t.dtype != dt:
-            raise MliisError("clip_apply {}: expected {} tensor, got {}".format(name, dt, t.dtype))
-        if t.device != table.chunks.device:
-            raise MliisError("clip_apply {}: on {}, the table on {}".format(name, t.device, table.chunks.device))
+    _log_tensors("clip_apply", (("grad", grad, torch.float32), ("ws", ws, None), ("cursor", cursor, torch.int32)) +
+                 ((("theta", theta, torch.float32),) if theta is not None else ()), table.chunks.device, "the table")
     _dense(grad, theta, ws, cursor, out)
     if grad.numel() != table.n or (theta is not None and theta.numel() != table.n):
         raise MliisError("clip_apply: grad has {} elements, theta {}, the table addresses {}".format(
@@ -1581,21 +1570,8 @@ def clip_apply(grad, theta, table: LayerTable, ws, cursor, mode, threshold, eps=
     threshold, eps = float(threshold), float(eps)
     if not (math.isfinite(threshold) and threshold > 0 and math.isfinite(eps) and eps > 0):
         raise MliisError("clip_apply: threshold = {!r}, eps = {!r} (finite and positive)".format(threshold, eps))
-    need = clip_lib.size("mliis_clip_workspace_bytes", table.nchunks, table.T)
-    if ws.element_size() != 4 or ws.numel() * 4 < need:
-        raise MliisError("clip_apply ws: {} bytes of 32-bit words needed (clip_workspace), got {} x {} bytes".format(
-            need, ws.numel(), ws.element_size()))
-    words, R = clip_lib.size("mliis_clip_record_words"), (table.T if mode == "ratio" else 1)
-    if out is None:
-        if capacity is None or int(capacity) < 1:
-            raise MliisError("clip_apply: capacity = {!r} (a ring of at least one row, or out=)".format(capacity))
-        out = torch.zeros((int(capacity), R, words), dtype=torch.int32, device=grad.device)
-    else:
-        if not torch.is_tensor(out) or not out.is_cuda or out.device != grad.device or out.dtype != torch.int32 or out.dim() != 3 or \
-                out.shape[1] != R or out.shape[2] != words or out.shape[0] < 1 or (capacity is not None and int(capacity) != out.shape[0]):
-            raise MliisError("clip_apply out: expected a device int32 ring of shape ({}, {}, {}), got {} {}".format(
-                "capacity" if capacity is None else int(capacity), R, words, tuple(out.shape) if torch.is_tensor(out) else out,
-                out.dtype if torch.is_tensor(out) else type(out)))
+    _log_workspace("clip_apply", ws, clip_lib.size("mliis_clip_workspace_bytes", table.nchunks, table.T))
+    out = _log_ring("clip_apply", out, capacity, (table.T if mode == "ratio" else 1, clip_lib.size("mliis_clip_record_words")), grad.device)
     _timed("clip_apply", {}, lambda: clip_lib.call(
         "mliis_clip_apply", _clip.MODES[mode], _ptr(grad), _ptr(theta), table.n, C.c_void_p(table.chunks.data_ptr()), table.nchunks,
         C.c_void_p(table.segs.data_ptr()), table.T, threshold, eps, C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(out.data_ptr()),

@@ -51,19 +51,31 @@ def capacity_for(steps_per_task: int) -> int:
     return max(MIN_CAPACITY, 1 << (n - 1).bit_length())
 
 
+def decode_ring(ring, cursor: int, last_cursor: int, dtype: np.dtype, row: Optional[str] = None) -> Tuple[np.ndarray, int]:
+    """The decoder of every device ring (this log's, layerlog.decode, clip.decode): (records, dropped) -- what was written between the
+    counter values last_cursor and cursor, oldest first, as a `dtype` array, and how many of those the ring no longer holds (more were
+    written than its capacity: the oldest are the ones lost).  The counters are taken modulo 2^32 like the device's.  row None: a ring
+    of [capacity, words] 32-bit words, records [kept]; row "T": one of [capacity, T, words] (the letter names the axis in the error),
+    records [kept, T]."""
+    words, n = np.ascontiguousarray(np.asarray(ring)).view(np.uint32), dtype.itemsize // 4
+    if row is None:
+        words = words.reshape(-1, n)
+        if words.shape[0] < 1:
+            raise ValueError("empty ring")
+    elif words.ndim != 3 or words.shape[2] != n or words.shape[0] < 1 or words.shape[1] < 1:
+        raise ValueError("expected a [capacity, {}, {}] ring, got {}".format(row, n, words.shape))
+    capacity = words.shape[0]
+    new = (int(cursor) - int(last_cursor)) & 0xFFFFFFFF
+    kept = min(new, capacity)
+    pos = (int(cursor) - kept + np.arange(kept, dtype=np.int64)) & 0xFFFFFFFF
+    return words[pos % capacity].copy().view(dtype).reshape((kept,) + words.shape[1:-1]), new - kept
+
+
 def decode(ring, cursor: int, last_cursor: int = 0) -> Tuple[np.ndarray, int]:
     """(records, dropped): the records appended between the counter values last_cursor and cursor, oldest first, as a RECORD_DTYPE array,
     and how many of them the ring no longer holds (more were appended than its capacity: the oldest are the ones lost).  ring: the
     [capacity, 8] 32-bit words read back from the device; the counters are taken modulo 2^32 like the device's."""
-    words = np.ascontiguousarray(np.asarray(ring)).view(np.uint32).reshape(-1, RECORD_WORDS)
-    capacity = words.shape[0]
-    if capacity < 1:
-        raise ValueError("empty ring")
-    new = (int(cursor) - int(last_cursor)) & 0xFFFFFFFF
-    kept = min(new, capacity)
-    pos = (int(cursor) - kept + np.arange(kept, dtype=np.int64)) & 0xFFFFFFFF
-    records = words[pos % capacity].copy().view(RECORD_DTYPE).reshape(-1)
-    return records, new - kept
+    return decode_ring(ring, cursor, last_cursor, RECORD_DTYPE)
 
 
 def nonfinite_steps(records: np.ndarray) -> np.ndarray:

@@ -143,7 +143,7 @@ def orchestrate(a):
              "One MI355X, `tools/bench_clip.py`: config 2 of `BASELINE.json` (EfficientLab-6-3, 224², meta-batch 1, 5 shots, 8 inner SGD steps of",
              "batch 8, fp32, captured graphs), inner-loop images/s of `Gecko.train_step`. Host clock around {} meta-steps that end in a device".format(t["steps"]),
              "synchronise, after {} untimed ones; every setting {} times, the settings alternating. Three processes, one after the other: the".format(t["warmup"], t["repeats"]),
-             "parent commit, this tree, the parent commit again (the parent has no `grad_clip`, so its two settings run).", "",
+             "parent commit, this tree, the parent commit again (a parent from before `grad_clip` runs the two settings it has).", "",
              "    python tools/bench_clip.py --parent <built checkout of the parent commit> --md profiles/clip.md --steps {} --warmup {} --repeats {}".format(
                  t["steps"], t["warmup"], t["repeats"]), "",
              "`--inner-clip-norm {}`, `--inner-clip-ratio {}` with eps {}.".format(t["clip_norm"], t["clip_ratio"], t["clip_ratio_eps"]), "",
