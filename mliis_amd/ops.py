@@ -1199,11 +1199,20 @@ def resize_bilinear_bwd(dy, in_hw, out=None, accumulate=False):
     return out
 
 
+def _mask_has_layout_of(what, mask, C_, ld):
+    """The final conv's kernels read the dropout mask with the leading dimension of x (include/mliis_hip.h: "mask has the layout of
+    x"), and the wrappers take a dense mask: beside a channel-slice view (ld > C) it would be read at the wrong rows and past its end."""
+    if mask is not None and ld != C_:
+        raise MliisError("{}: a mask needs a dense activation tensor (leading dimension {} != {} channels: the kernel would read the "
+                         "dense mask with the view's row stride)".format(what, ld, C_))
+
+
 def final_conv_fwd(x, w, b, mask=None, out=None):
     rows, C_, ldx = rows_ld(x)
     _dense(w, b, mask)
     if mask is not None and mask.numel() != rows * C_:
         raise MliisError("final_conv_fwd: mask must be a dense [rows, {}] tensor, got {}".format(C_, tuple(mask.shape)))
+    _mask_has_layout_of("final_conv_fwd", mask, C_, ldx)
     _out_dense(out, tuple(x.shape[:-1]) + (2,), what="final_conv_fwd out")
     out = torch.empty(tuple(x.shape[:-1]) + (2,), dtype=torch.float32, device=x.device) if out is None else out
     lib.call("mliis_final_conv_fwd", _ptr(x), ldx, _ptr(mask), _ptr(w), _ptr(b), _ptr(out), rows, C_, _stream())
@@ -1219,6 +1228,7 @@ def final_conv_bwd_data(dy, w, C_, mask=None, out=None, fin=None):
     _out_rows(out, tuple(dy.shape[:-1]) + (C_,), what="final_conv_bwd_data out")
     out = torch.empty(tuple(dy.shape[:-1]) + (C_,), dtype=torch.float32, device=dy.device) if out is None else out
     _, _, lddx = rows_ld(out)
+    _mask_has_layout_of("final_conv_bwd_data", mask, C_, lddx)
     if fin is not None:
         buf, size, extra_loss, loss_out = fin
         N, Hd, Wd = dy.shape[:3]
@@ -1234,6 +1244,7 @@ def final_conv_bwd_filter(x, dy, mask=None, dw=None, db=None, ws: Optional[Works
     _dense(dy, mask)
     if mask is not None and mask.numel() != rows * C_:
         raise MliisError("final_conv_bwd_filter: mask must be a dense [rows, {}] tensor, got {}".format(C_, tuple(mask.shape)))
+    _mask_has_layout_of("final_conv_bwd_filter", mask, C_, ldx)
     _out_dense(dw, (1, 1, C_, 2), what="final_conv_bwd_filter dw")
     _out_dense(db, (2,), what="final_conv_bwd_filter db")
     dw = torch.empty((1, 1, C_, 2), dtype=torch.float32, device=x.device) if dw is None else dw
