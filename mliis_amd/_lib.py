@@ -175,6 +175,18 @@ SWEEP_SIGNATURES = {
     "mliis_prob_histogram": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }
 
+# libmliis_loss.so (include/mliis_loss.h): the focal, foreground-weighted pixel loss of the inner loop, a library of its own as well; loaded
+# only by a learner built with focal_gamma != 0 or fg_weight != 1
+LOSS_LIB_PATH = os.path.join(_HERE, "libmliis_loss.so")
+LOSS_SIGNATURES = {
+    "mliis_loss_last_error": (C.c_char_p, []),
+    "mliis_focal_ce_workspace_floats": (_sz, [_i, _i, _i]),
+    "mliis_focal_ce": (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, _i, _f, _p, _p, _p, _sz, _p]),
+    "mliis_head_focal_fused_supported": (_i, [_i, _i, _i, _i]),
+    "mliis_head_focal_fused_workspace_floats": (_sz, [_i, _i, _i]),
+    "mliis_head_focal_fused": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _sz, _p]),
+}
+
 
 class MliisError(RuntimeError):
     pass
@@ -183,7 +195,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib, sweep_lib)."""
+        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib, sweep_lib, loss_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -231,3 +243,4 @@ steplog_lib = _Lib(STEPLOG_LIB_PATH, STEPLOG_SIGNATURES, "mliis_steplog_last_err
 layerlog_lib = _Lib(LAYERLOG_LIB_PATH, LAYERLOG_SIGNATURES, "mliis_layerlog_last_error")
 clip_lib = _Lib(CLIP_LIB_PATH, CLIP_SIGNATURES, "mliis_clip_last_error")
 sweep_lib = _Lib(SWEEP_LIB_PATH, SWEEP_SIGNATURES, "mliis_sweep_last_error")
+loss_lib = _Lib(LOSS_LIB_PATH, LOSS_SIGNATURES, "mliis_loss_last_error")

@@ -27,6 +27,18 @@ def _positive_float(v) -> float:
     return f
 
 
+def _nonnegative_float(v) -> float:
+    """argparse type of an exponent: a finite float at or above zero."""
+    import math
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise argparse.ArgumentTypeError("{!r} is not a number".format(v)) from None
+    if not (math.isfinite(f) and f >= 0):
+        raise argparse.ArgumentTypeError("{!r} is not a finite number >= 0".format(v))
+    return f
+
+
 _FLAGS = [
     ("--fine-tune-task", dict(type=str, default=None)),
     ("--fine-tuned-checkpoint", dict(type=str, default=None)),
@@ -186,6 +198,16 @@ _EXT = [
     ("--inner-clip-ratio-eps", dict(type=_positive_float, default=1e-3, metavar="EPS",
                                     help="with --inner-clip-ratio: the floor of ||theta_t||, which lets zero-initialised biases and "
                                          "batch-norm betas move")),
+    ("--focal-gamma", dict(type=_nonnegative_float, default=None, metavar="G",
+                           help="focal modulation of the inner loop's pixel loss (Lin et al.): every pixel's cross-entropy term of class c "
+                                "times (1 - p_c)^G, on the device (csrc/focal.hip: the fused head's counterpart, one launch more per "
+                                "step).  0 is the cross-entropy.  Composes with --loss_name bce_dice, --label_smoothing, --l2, --l1, "
+                                "--darc1 and --fg-weight; applies wherever a model is adapted (the same places as --inner-clip-norm); "
+                                "evaluation and prediction are unchanged.  `ce` in inner_loop.jsonl is then the focal pixel term")),
+    ("--fg-weight", dict(type=_positive_float, default=None, metavar="W",
+                         help="weight of the foreground pixels in the inner loop's pixel loss: a pixel counts 1 + (W - 1) * label.  The sum is "
+                              "still divided by N H W, not by the sum of the weights, so W > 1 raises the loss scale and usually wants a "
+                              "smaller --learning-rate or a clip.  The same kernels and places as --focal-gamma")),
     ("--threshold-sweep", dict(action="store_true",
                                help="sweep the decision threshold in the final evaluation pass over the meta-test (or, with "
                                     "--eval_val_tasks, meta-val) tasks: every test image leaves a 2 x 256 histogram of its foreground "
@@ -213,6 +235,17 @@ def grad_clip(a):
     if lam is not None:
         return ("ratio", _positive_float(lam), _positive_float(getattr(a, "inner_clip_ratio_eps", 1e-3)))
     return None
+
+
+def focal_loss(a) -> dict:
+    """The `focal_gamma` / `fg_weight` arguments of the Learner from --focal-gamma / --fg-weight: only the keys whose flag was given."""
+    g, w = getattr(a, "focal_gamma", None), getattr(a, "fg_weight", None)
+    out = {}
+    if g is not None:
+        out["focal_gamma"] = _nonnegative_float(g)
+    if w is not None:
+        out["fg_weight"] = _positive_float(w)
+    return out
 
 
 def threshold_sweep(a):
@@ -287,6 +320,7 @@ def model_kwargs(a) -> dict:
     clip = grad_clip(a)
     if clip is not None:   # (absent without the flags as well; its ring holds the steps of one task like the step log's)
         log.update(grad_clip=clip, clip_log=capacity_for(steps))
+    log.update(focal_loss(a))   # (absent without the flags as well)
     return dict(feature_extractor_name=a.feature_extractor_name, image_size=a.image_size, rsd=a.rsd or None,
                 learning_rate=a.learning_rate, optimizer="sgd" if a.sgd else "adam", l2=a.l2, l1=a.l1, darc1=a.darc1,
                 dice=("dice" in a.loss_name), label_smoothing=a.label_smoothing, final_layer_dropout_rate=a.final_layer_dropout_rate,

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -31,7 +32,7 @@ import torch
 from . import ops, spec
 from . import clip as clip_mod
 from . import layerlog
-from ._lib import MliisError, clip_lib, layerlog_lib, lib, score_lib, steplog_lib, sweep_lib
+from ._lib import MliisError, clip_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
@@ -54,12 +55,26 @@ class Learner(_Passes):
                  spatial_pyramid_pooling: bool = False, skip_decoding: bool = False, drop_connect: bool = True, seed: int = 0,
                  device="cuda:0", use_graph: bool = True, max_shots: int = 16, matmul_precision: str = "fp32",
                  small_fused: Optional[bool] = None, dw_march: Optional[bool] = None, fuse_bn2: Optional[bool] = None, fuse_head: Optional[bool] = None,
-                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False, grad_clip=None, clip_log: int = 0):
+                 augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False, grad_clip=None, clip_log: int = 0,
+                 focal_gamma: float = 0.0, fg_weight: float = 1.0):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam' (Adam with beta1=0, the reference default)")
         if not torch.cuda.is_available():
             raise MliisError("mliis_amd.Learner needs an MI355X (HIP device); there is no CPU path")
         lib.load()  # fail loudly if the HIP extension is missing
+        # focal_gamma G >= 0, fg_weight W > 0: the pixel term of the loss becomes -w (t0 p1^G l0 + t1 p0^G l1) with w = 1 + (W - 1) y1, over
+        # N H W (include/mliis_loss.h) -- ops.head_focal_fused / ops.focal_ce where the step issues ops.head_ce_fused / ops.softmax_ce.
+        # Active only when one of the two differs from its default; then the library is loaded here (a missing library is an error here,
+        # not at the first step).  The scalars are by-value kernel arguments, captured into the step's graph: fixed at construction.
+        # Inactive (the default): nothing is loaded or allocated and the step's launches are what they were.
+        self.focal_gamma, self.fg_weight = float(focal_gamma), float(fg_weight)
+        if not (math.isfinite(self.focal_gamma) and self.focal_gamma >= 0.0):
+            raise ValueError("focal_gamma must be a finite float >= 0, got {!r}".format(focal_gamma))
+        if not (math.isfinite(self.fg_weight) and self.fg_weight > 0.0):
+            raise ValueError("fg_weight must be a finite float > 0, got {!r}".format(fg_weight))
+        self.focal = self.focal_gamma != 0.0 or self.fg_weight != 1.0
+        if self.focal:
+            loss_lib.load()
         # operand precision of the matrix cores in the dense convs: "fp32" (BASELINE configs 1-3) or "bf16" (operands rounded to bf16 on
         # the fly, fp32 accumulation; everything else stays fp32).  Passed with every dense-conv call (nothing process-wide).
         # "bf16-storage" (BASELINE configs[3]): bf16 operands AND the expanded tensors of the MBConv blocks (z0, z1, a1 and their
@@ -579,17 +594,27 @@ class Learner(_Passes):
         # Without the dice term (and DARC1, which reads the full-resolution logits) the tail of the step -- resize to the image size,
         # softmax cross-entropy, its gradient, the resize's transpose -- is ONE launch on the decoder's map (ops.head_ce_fused)
         hd_, H_ = self.arch.h_dec, self.arch.image_size
-        head_fused = bool(self.fuse_head and not self.dice and not self.darc1 and lib.size("mliis_head_ce_fused_supported", hd_, hd_, H_, H_))
+        hlib, hname = (loss_lib, "mliis_head_focal_fused") if self.focal else (lib, "mliis_head_ce_fused")
+        head_fused = bool(self.fuse_head and not self.dice and not self.darc1 and hlib.size(hname + "_supported", hd_, hd_, H_, H_))
         logits = self._forward(P, self.shots_x, P.idx, True, upsample=not head_fused)
-        if head_fused:   # ONE launch: the fold of the loss partials rides in the final conv's backward-data launch (passes.py)
+        if head_fused:
             if P.head_ws is None:
-                P.head_ws = ops.Workspace(self.device, lib.size("mliis_head_ce_fused_workspace_floats", P.N, hd_, hd_))
-            _, _, buf = ops.head_ce_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, P.dsmall, P.loss_out, ws=P.head_ws,
-                                          finalize=False)
-            P.head_fin = (buf, (H_, H_), 0.0, P.loss_out)
+                P.head_ws = ops.Workspace(self.device, hlib.size(hname + "_workspace_floats", P.N, hd_, hd_))
+            if self.focal:   # TWO launches: the focal head and its own fold (the other library's backward-data launch cannot fold for it)
+                ops.head_focal_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, self.focal_gamma, self.fg_weight, P.dsmall,
+                                     P.loss_out, ws=P.head_ws)
+                P.head_fin = None
+            else:   # ONE launch: the fold of the loss partials rides in the final conv's backward-data launch (passes.py)
+                _, _, buf = ops.head_ce_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, P.dsmall, P.loss_out, ws=P.head_ws,
+                                              finalize=False)
+                P.head_fin = (buf, (H_, H_), 0.0, P.loss_out)
         else:
-            ops.softmax_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.dice, 0.0, want_grad=True, want_pred=False,
-                           dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
+            if self.focal:
+                ops.focal_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.focal_gamma, self.fg_weight, self.dice, 0.0, want_grad=True,
+                             dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
+            else:
+                ops.softmax_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.dice, 0.0, want_grad=True, want_pred=False,
+                               dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
             if self.darc1:
                 ops.darc1(logits, spec.L2_WEIGHT, dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
         self._backward(P, self.shots_x, P.idx, head_fused=head_fused)

@@ -17,7 +17,7 @@ import torch
 
 from . import clip as _clip
 from . import layerlog as _layerlog
-from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, score_lib, steplog_lib, sweep_lib
+from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1287,6 +1287,40 @@ def head_ce_fused(small, labels, idx, size, label_smoothing, dsmall, out, extra_
                                                  float(label_smoothing), float(extra_loss), _ptr(dsmall), _ptr(out) if finalize else None, _ptr(buf),
                                                  buf.numel(), _stream()))
     return (out, dsmall) if finalize else (out, dsmall, buf)
+
+
+def focal_ce(logits, labels, idx=None, label_smoothing=0.0, gamma=0.0, fg_weight=1.0, dice=False, extra_loss=0.0, want_grad=True, dlogits=None,
+             out=None, ws: Optional[Workspace] = None):
+    """softmax_ce's counterpart for the focal, foreground-weighted pixel loss (libmliis_loss.so, include/mliis_loss.h, csrc/focal.hip):
+    per pixel -w (t0 p1^gamma l0 + t1 p0^gamma l1) with w = 1 + (fg_weight - 1) y1, summed and divided by N H W; the dice term, label
+    smoothing and extra_loss compose as in softmax_ce.  out[0..2] = {loss, the pixel term, iou}; dlogits as there.  No prediction mask."""
+    N, H, W, _ = logits.shape
+    dev = logits.device
+    _dense(logits, labels, idx)
+    _out_dense(dlogits, tuple(logits.shape), what="focal_ce dlogits")
+    if want_grad and dlogits is None:
+        dlogits = torch.empty_like(logits)
+    out = torch.empty(4, dtype=torch.float32, device=dev) if out is None else out
+    ws = ws or default_ws()
+    buf = ws.get(loss_lib.size("mliis_focal_ce_workspace_floats", N, H, W))
+    _timed("focal_ce", {}, lambda: loss_lib.call("mliis_focal_ce", _ptr(_chk(logits)), _ptr(_chk(labels)), _ptr(idx), N, H, W, float(label_smoothing),
+                                                 float(gamma), float(fg_weight), int(dice), float(extra_loss), _ptr(dlogits) if want_grad else None,
+                                                 _ptr(_chk(out)), _ptr(buf), buf.numel(), _stream()))
+    return out, dlogits
+
+
+def head_focal_fused(small, labels, idx, size, label_smoothing, gamma, fg_weight, dsmall, out, extra_loss=0.0, ws: Optional[Workspace] = None):
+    """head_ce_fused's counterpart for the same loss: resize(small -> size) -> focal_ce (no dice term) -> gradient -> resize^T as the tile
+    launch and its fold (two launches; the full-resolution logits are never written): dsmall and out[0..2] = {loss, the pixel term, iou}."""
+    N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx)
+    _out_dense(dsmall, tuple(small.shape), what="head_focal_fused dsmall")
+    ws = ws or default_ws()
+    buf = ws.get(loss_lib.size("mliis_head_focal_fused_workspace_floats", N, Hd, Wd))
+    _timed("head_focal_fused", {}, lambda: loss_lib.call("mliis_head_focal_fused", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd,
+                                                         int(size[0]), int(size[1]), float(label_smoothing), float(gamma), float(fg_weight),
+                                                         float(extra_loss), _ptr(_chk(dsmall)), _ptr(_chk(out)), _ptr(buf), buf.numel(), _stream()))
+    return out, dsmall
 
 
 def mask_iou_counts(small, labels, idx, size, counts=None):
