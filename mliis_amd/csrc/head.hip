@@ -5,6 +5,7 @@
 // :294-303,319-327,329-396 (loss).  All HBM-bound, all deterministic (gather-form backward, two-stage reductions).
 #include "common.hpp"
 #include "head_math.hpp"
+#include "loss_kernels.hpp"
 
 namespace mliis {
 
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256) void final_conv_fwd_k(const float* __restrict_
 }
 
 // fin_part != nullptr (mliis_final_conv_bwd_data_fin): workgroup 0 first folds the loss partials the fused head launch left behind
-// (ce_finalize: out[0..2] = {loss, ce, iou}) -- the fold needs nothing of this kernel and nothing of the step waits for it, so it
+// (loss_fold: out[0..2] = {loss, ce, iou}) -- the fold needs nothing of this kernel and nothing of the step waits for it, so it
 // rides here instead of in a launch of its own between the head and the backward pass.
 struct CeFin {
   const float* part;
@@ -193,12 +194,10 @@ struct CeFin {
   float* out;
   float* coef;
 };
-__device__ __forceinline__ void ce_finalize(const float* __restrict__ part, int nblk, int N, int HW, int dice, float extra_loss, float* __restrict__ out,
-                                            float* __restrict__ coef);
 __global__ __launch_bounds__(256) void final_conv_bwd_data_k(const float* __restrict__ dy, const float* __restrict__ w,
                                                              const float* __restrict__ mask, float* __restrict__ dx, int lddx,
                                                              long long rows, int C, CeFin fin) {
-  if (fin.part != nullptr && blockIdx.x == 0) ce_finalize(fin.part, fin.nblk, fin.N, fin.HW, 0, fin.extra_loss, fin.out, fin.coef);   // (uniform)
+  if (fin.part != nullptr && blockIdx.x == 0) loss_fold(fin.part, fin.nblk, fin.N, fin.HW, 0, fin.extra_loss, fin.out, fin.coef);   // (uniform)
   const int Q = C >> 2;
   const long long total = rows * Q;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -213,257 +212,66 @@ __global__ __launch_bounds__(256) void final_conv_bwd_data_k(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ softmax CE (+dice)
-// part layout [n][blk][4] = {sum CE, sum p1*t1, sum p1, sum t1}
+// The cross-entropy's per-pixel policy for the kernel bodies of loss_kernels.hpp.  The softmax pair of the gradient and of the prediction
+// mask is softmax2's (head_math.hpp: score.hip's mask is pinned to it, e1 * inv); the loss terms take p1 as e1 / (e0 + e1) and form m, e0,
+// e1 and lse themselves, only where the terms are asked for.  Fused: the fused head's instantiation, where the two halves of a packed
+// pair pass through lone() (common.hpp) before they are summed and the sum is broadcast back over the pair.
+template <bool Fused>
+struct CePixel {
+  float ls, inv_rows;
+  struct At {
+    float2 zz, tt;
+    float t0, t1, p0, p1;
+  };
+  __device__ __forceinline__ At at(float2 zz, float2 tt) const {
+    At a;
+    a.zz = zz;
+    a.tt = tt;
+    softmax2(zz, a.p0, a.p1);
+    a.t0 = tt.x * (1.f - ls) + 0.5f * ls, a.t1 = tt.y * (1.f - ls) + 0.5f * ls;
+    return a;
+  }
+  __device__ __forceinline__ float2 grad(const At& a) const {
+    const float ts = Fused ? lone(a.t0) + lone(a.t1) : a.t0 + a.t1;
+    return make_float2((a.p0 * ts - a.t0) * inv_rows, (a.p1 * ts - a.t1) * inv_rows);
+  }
+  __device__ __forceinline__ float2 with_dice(float2 g, float dp1) const { return make_float2(g.x - dp1, g.y + dp1); }
+  __device__ __forceinline__ void terms(const At& a, float& ce, float& I, float& Sp, float& St) const {
+    const float m = fmaxf(a.zz.x, a.zz.y);
+    const float e0 = expf(a.zz.x - m), e1 = expf(a.zz.y - m);
+    const float lse = m + logf(e0 + e1);
+    ce -= a.t0 * (a.zz.x - lse) + a.t1 * (a.zz.y - lse);
+    const float q1 = e1 / (e0 + e1);
+    I += q1 * a.tt.y;
+    Sp += q1;
+    St += a.tt.y;
+  }
+};
+
 __global__ __launch_bounds__(256) void ce_partial_k(const float* __restrict__ logits, const float* __restrict__ labels,
                                                     const int* __restrict__ idx, int HW, float ls, float* __restrict__ part) {
-  __shared__ float sm[4][4];
-  const int n = blockIdx.y;
-  const int src = idx ? idx[n] : n;
-  const float* z = logits + (long long)n * HW * 2;
-  const float* t = labels + (long long)src * HW * 2;
-  float ce = 0.f, I = 0.f, Sp = 0.f, St = 0.f;
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const float2 zz = *reinterpret_cast<const float2*>(z + (long long)p * 2);
-    const float2 tt = *reinterpret_cast<const float2*>(t + (long long)p * 2);
-    const float m = fmaxf(zz.x, zz.y);
-    const float e0 = expf(zz.x - m), e1 = expf(zz.y - m);
-    const float lse = m + logf(e0 + e1);
-    const float t0 = tt.x * (1.f - ls) + 0.5f * ls, t1 = tt.y * (1.f - ls) + 0.5f * ls;
-    ce -= t0 * (zz.x - lse) + t1 * (zz.y - lse);
-    const float p1 = e1 / (e0 + e1);
-    I += p1 * tt.y;
-    Sp += p1;
-    St += tt.y;
-  }
-  ce = wave_sum(ce);
-  I = wave_sum(I);
-  Sp = wave_sum(Sp);
-  St = wave_sum(St);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sm[wave][0] = ce;
-    sm[wave][1] = I;
-    sm[wave][2] = Sp;
-    sm[wave][3] = St;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const float s = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
-    part[((long long)n * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = s;
-  }
-}
-
-// out: [0] loss, [1] ce, [2] iou ; coef[n] = {A_n, B_n} for the dice gradient (0 when dice off).  One block: 8 images at a time,
-// 32 lanes per image fold that image's partial blocks (double precision), a lane butterfly finishes the image, thread 0 adds the
-// images up in index order (fixed order: deterministic).
-__device__ __forceinline__ void ce_finalize(const float* __restrict__ part, int nblk, int N, int HW, int dice, float extra_loss,
-                                            float* __restrict__ out, float* __restrict__ coef) {
-  __shared__ double s_ce[8], s_iou[8];
-  double ce = 0.0, iou = 0.0;
-  const double eps = 1e-7;
-  const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
-  for (int n0 = 0; n0 < N; n0 += 8) {
-    const int n = n0 + g;
-    double v[4] = {0, 0, 0, 0};
-    if (n < N)
-      for (int b = lane; b < nblk; b += 32) {
-        const float4 q = ld4(part + ((long long)n * nblk + b) * 4);
-        v[0] += q.x;
-        v[1] += q.y;
-        v[2] += q.z;
-        v[3] += q.w;
-      }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int off = 1; off < 32; off <<= 1) v[k] += __shfl_xor(v[k], off);
-    if (lane == 0 && n < N) {
-      const double I = v[1], Sp = v[2], St = v[3];
-      const double U = Sp + St - I;
-      s_ce[g] = v[0];
-      s_iou[g] = (I + eps) / (U + eps);
-      coef[2 * n + 0] = (float)(1.0 / (U + eps));
-      coef[2 * n + 1] = (float)((I + eps) / ((U + eps) * (U + eps)));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int j = 0; j < 8 && n0 + j < N; ++j) {
-        ce += s_ce[j];
-        iou += s_iou[j];
-      }
-    __syncthreads();
-  }
-  if (threadIdx.x != 0) return;
-  ce /= (double)N * HW;
-  iou /= N;
-  double loss = ce + extra_loss;
-  double dLdiou = 0.0;
-  if (dice) {
-    loss -= log(2.0 * iou / (iou + 1.0));
-    dLdiou = -1.0 / (iou * (iou + 1.0));
-  }
-  for (int n = 0; n < N; ++n) {
-    coef[2 * n + 0] = (float)(coef[2 * n + 0] * dLdiou / N);
-    coef[2 * n + 1] = (float)(coef[2 * n + 1] * dLdiou / N);
-  }
-  out[0] = (float)loss;
-  out[1] = (float)ce;
-  out[2] = (float)iou;
+  loss_partial(CePixel<false>{ls, 0.f}, logits, labels, idx, HW, part);
 }
 
 __global__ __launch_bounds__(256) void ce_finalize_k(const float* __restrict__ part, int nblk, int N, int HW, int dice, float extra_loss,
                                                      float* __restrict__ out, float* __restrict__ coef) {
-  ce_finalize(part, nblk, N, HW, dice, extra_loss, out, coef);
+  loss_fold(part, nblk, N, HW, dice, extra_loss, out, coef);
 }
 
-// fin_part != nullptr (no dice term: the gradient needs nothing from the finalize step): workgroup (0, 0) also folds the loss partials
-// into out[] before its share of the gradient -- one launch fewer than ce_partial -> ce_finalize -> ce_grad.
 __global__ __launch_bounds__(256) void ce_grad_k(const float* __restrict__ logits, const float* __restrict__ labels,
                                                  const int* __restrict__ idx, int HW, float ls, float inv_rows,
                                                  const float* __restrict__ coef, float* __restrict__ dlogits,
                                                  float* __restrict__ pred, const float* __restrict__ fin_part, int fin_nblk, int N,
                                                  float extra_loss, float* __restrict__ fin_out, float* __restrict__ fin_coef) {
-  if (fin_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) ce_finalize(fin_part, fin_nblk, N, HW, 0, extra_loss, fin_out, fin_coef);
-  const int n = blockIdx.y;
-  const int src = idx ? idx[n] : n;
-  const float* z = logits + (long long)n * HW * 2;
-  const float* t = labels + (long long)src * HW * 2;
-  const float An = fin_part != nullptr ? 0.f : coef[2 * n], Bn = fin_part != nullptr ? 0.f : coef[2 * n + 1];
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const float2 zz = *reinterpret_cast<const float2*>(z + (long long)p * 2);
-    const float2 tt = *reinterpret_cast<const float2*>(t + (long long)p * 2);
-    float p0, p1;
-    softmax2(zz, p0, p1);
-    const float t0 = tt.x * (1.f - ls) + 0.5f * ls, t1 = tt.y * (1.f - ls) + 0.5f * ls;
-    const float ts = t0 + t1;
-    float d0 = (p0 * ts - t0) * inv_rows, d1 = (p1 * ts - t1) * inv_rows;
-    const float dp1 = (An * tt.y - Bn * (1.f - tt.y)) * p1 * (1.f - p1);
-    d1 += dp1;
-    d0 -= dp1;
-    if (dlogits) *reinterpret_cast<float2*>(dlogits + ((long long)n * HW + p) * 2) = make_float2(d0, d1);
-    if (pred) *reinterpret_cast<float2*>(pred + ((long long)n * HW + p) * 2) = make_float2(p0 > 0.5f ? 1.f : 0.f, p1 > 0.5f ? 1.f : 0.f);
-  }
+  loss_grad(CePixel<false>{ls, inv_rows}, logits, labels, idx, HW, coef, dlogits, pred, fin_part, fin_nblk, N, extra_loss, fin_out, fin_coef);
 }
 
-// ------------------------------------------------------------------------------------------------ resize -> softmax CE -> resize^T, one pass
-// The tail of a training step without the dice term: logits = resize(small) (models/efficientlab.py:166-173), per-pixel softmax
-// cross-entropy (:294-303), its gradient (p - t) / (N H W) -- which needs no global sum -- and the transpose of the resize back to
-// the decoder's map.  A workgroup owns an 8 x 8 tile of DECODER pixels:
-//   phase 1: every image pixel that a pixel of the tile reaches (the tile's footprint, <= kHeadFoot^2 pixels) gets its logits rebuilt
-//            from the four decoder pixels around it (resize_fwd_k's arithmetic) and its gradient formed (ce_grad_k's arithmetic) into
-//            LDS; the loss terms of an image pixel are added by the tile that holds its top-left source pixel (one owner each);
-//   phase 2: the 8 lanes of a decoder pixel walk its candidates exactly as resize_bwd_k does, reading the gradients from LDS.
-// The full-resolution logits / gradient tensors are never written (four launches and 4 x 3.2 MB of traffic at 224x224, N = 8, become
-// two).  Loss partials per workgroup [n][tile][4] as ce_partial_k's, folded by ce_finalize_k -- a launch of its own: a last-arriver
-// fold inside this kernel needs device-scope fences, which on this eight-L2 part write back and invalidate a whole L2 each
-// (measured: 39 us for the launch, more than the four it replaces).  (A first form without the LDS phase -- every decoder pixel
-// rebuilding its ~100 candidates itself -- took 69 us: one dependent load chain per candidate.)
-constexpr int kHeadTile = 8, kHeadFoot = 48;
-__device__ __forceinline__ int head_lo(int i, float s) {
-  const int v = (int)floorf((float)(i - 1) / s) - 1;
-  return v < 0 ? 0 : v;
-}
-__device__ __forceinline__ int head_hi(int i, float s, int n) {
-  const int v = (int)ceilf((float)(i + 1) / s) + 1;
-  return v > n - 1 ? n - 1 : v;
-}
+// resize -> softmax CE -> resize^T in one pass (loss_kernels.hpp, head_fused_tile)
 __global__ __launch_bounds__(256) void head_ce_fused_k(const float* __restrict__ small, const float* __restrict__ labels,
                                                        const int* __restrict__ idx, int N, int Hi, int Wi, int Ho, int Wo, float sh, float sw,
                                                        float ls, float inv_rows, float* __restrict__ dsmall, float* __restrict__ part,
                                                        int tiles_x) {
-  __shared__ float2 gl[kHeadFoot * kHeadFoot];
-  __shared__ float sm[4][4];
-  const int t = threadIdx.x;
-  const int n = blockIdx.y;
-  const int src = idx ? idx[n] : n;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int hi0 = ty * kHeadTile, wi0 = tx * kHeadTile;
-  const int hi1 = hi0 + kHeadTile - 1 < Hi - 1 ? hi0 + kHeadTile - 1 : Hi - 1;
-  const int wi1 = wi0 + kHeadTile - 1 < Wi - 1 ? wi0 + kHeadTile - 1 : Wi - 1;
-  const int fo0 = head_lo(hi0, sh), fo1 = head_hi(hi1, sh, Ho), fw0 = head_lo(wi0, sw), fw1 = head_hi(wi1, sw, Wo);
-  const int FH = fo1 - fo0 + 1, FW = fw1 - fw0 + 1;   // (host: <= kHeadFoot)
-  const float* zb = small + (long long)n * Hi * Wi * 2;
-  const float* tb = labels + (long long)src * Ho * Wo * 2;
-  float ce = 0.f, I = 0.f, Sp = 0.f, St = 0.f;
-  for (int p = t; p < FH * FW; p += 256) {
-    const int fr = p / FW, fc = p - fr * FW;
-    const int ho = fo0 + fr, wo = fw0 + fc;
-    int y0, y1, x0, x1;
-    float ly, lx;
-    src_coord(ho, sh, Hi, y0, y1, ly);
-    src_coord(wo, sw, Wi, x0, x1, lx);
-    const float2 tl = *reinterpret_cast<const float2*>(zb + ((long long)y0 * Wi + x0) * 2);
-    const float2 tr = *reinterpret_cast<const float2*>(zb + ((long long)y0 * Wi + x1) * 2);
-    const float2 bl = *reinterpret_cast<const float2*>(zb + ((long long)y1 * Wi + x0) * 2);
-    const float2 br = *reinterpret_cast<const float2*>(zb + ((long long)y1 * Wi + x1) * 2);
-    const float2 tt = *reinterpret_cast<const float2*>(tb + ((long long)ho * Wo + wo) * 2);
-    float2 zz = make_float2(0.f, 0.f);
-    float wtl, wtr, wbl, wbr;
-    bilinear_weights(ly, lx, wtl, wtr, wbl, wbr);
-    zz = vfma(wtl, tl, zz);
-    zz = vfma(wtr, tr, zz);
-    zz = vfma(wbl, bl, zz);
-    zz = vfma(wbr, br, zz);
-    const float m = fmaxf(zz.x, zz.y);
-    const float e0 = expf(zz.x - m), e1 = expf(zz.y - m);
-    const float inv = 1.f / (e0 + e1);
-    const float p0 = e0 * inv, p1 = e1 * inv;
-    const float t0 = tt.x * (1.f - ls) + 0.5f * ls, t1 = tt.y * (1.f - ls) + 0.5f * ls;
-    const float ts = lone(t0) + lone(t1);   // (the sum of the two halves of a packed pair, broadcast back over the pair: common.hpp, lone())
-    gl[fr * kHeadFoot + fc] = make_float2((p0 * ts - t0) * inv_rows, (p1 * ts - t1) * inv_rows);
-    if (y0 >= hi0 && y0 <= hi1 && x0 >= wi0 && x0 <= wi1) {   // this tile owns the image pixel's loss terms
-      const float lse = m + logf(e0 + e1);
-      ce -= t0 * (zz.x - lse) + t1 * (zz.y - lse);
-      const float q1 = e1 / (e0 + e1);
-      I += q1 * tt.y;
-      Sp += q1;
-      St += tt.y;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int pg = (t >> 3) + 32 * it, rl = t & 7;
-    const int hi = hi0 + pg / kHeadTile, wi = wi0 + pg % kHeadTile;
-    const bool live = hi <= hi1 && wi <= wi1;
-    const int hc = live ? hi : hi0, wc = live ? wi : wi0;
-    const int ho_lo = head_lo(hc, sh), ho_hi = head_hi(hc, sh, Ho), wo_lo = head_lo(wc, sw), wo_hi = head_hi(wc, sw, Wo);
-    float2 acc = make_float2(0.f, 0.f);
-    for (int ho = ho_lo + rl; ho <= ho_hi; ho += 8) {
-      int y0, y1;
-      float ly;
-      src_coord(ho, sh, Hi, y0, y1, ly);
-      const float wy = (y0 == hc ? 1.f - ly : 0.f) + (y1 == hc ? ly : 0.f);
-      if (wy == 0.f) continue;
-      const float2* row = gl + (ho - fo0) * kHeadFoot - fw0;
-      for (int wo = wo_lo; wo <= wo_hi; ++wo) {
-        int x0, x1;
-        float lx;
-        src_coord(wo, sw, Wi, x0, x1, lx);
-        const float wx = (x0 == wc ? 1.f - lx : 0.f) + (x1 == wc ? lx : 0.f);
-        acc = vfma(wy * wx, row[wo], acc);
-      }
-    }
-#pragma unroll
-    for (int off = 1; off < 8; off <<= 1) {
-      acc.x += __shfl_xor(acc.x, off);
-      acc.y += __shfl_xor(acc.y, off);
-    }
-    if (live && rl == 0) *reinterpret_cast<float2*>(dsmall + ((long long)n * Hi * Wi + (long long)hi * Wi + wi) * 2) = acc;
-  }
-  ce = wave_sum(ce);
-  I = wave_sum(I);
-  Sp = wave_sum(Sp);
-  St = wave_sum(St);
-  const int lane = t & 63, wave = t >> 6;
-  if (lane == 0) {
-    sm[wave][0] = ce;
-    sm[wave][1] = I;
-    sm[wave][2] = Sp;
-    sm[wave][3] = St;
-  }
-  __syncthreads();
-  if (t < 4) part[((long long)n * gridDim.x + blockIdx.x) * 4 + t] = sm[0][t] + sm[1][t] + sm[2][t] + sm[3][t];
+  head_fused_tile(CePixel<true>{ls, inv_rows}, small, labels, idx, Hi, Wi, Ho, Wo, sh, sw, dsmall, part, tiles_x);
 }
 
 // ------------------------------------------------------------------------------------------------ DARC1 regulariser
@@ -668,7 +476,6 @@ int mliis_final_conv_bwd_data(const float* dy, const float* w, const float* mask
   return MLIIS_OK;
 }
 
-static inline int head_tiles(int n);
 // mliis_final_conv_bwd_data + the loss fold of a mliis_head_ce_fused call that was given out == NULL: fin_ws = that call's workspace
 // (untouched since), (N, Hd, Wd, H, W, extra_loss) as given there; out[0..2] = {loss + extra_loss, ce, iou}.
 int mliis_final_conv_bwd_data_fin(const float* dy, const float* w, const float* mask, float* dx, int lddx, long long rows, int C, float* fin_ws,
@@ -684,12 +491,7 @@ int mliis_final_conv_bwd_data_fin(const float* dy, const float* w, const float* 
   return MLIIS_OK;
 }
 
-size_t mliis_softmax_ce_workspace_floats(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return 0;
-  int nblk = ceil_div((long long)H * W, 256 * 8);
-  if (nblk > 256) nblk = 256;
-  return (size_t)N * nblk * 4 + 2 * (size_t)N + 8;
-}
+size_t mliis_softmax_ce_workspace_floats(int N, int H, int W) { return loss_workspace_floats(N, H, W); }
 
 // logits [N,H,W,2]; labels [S,H,W,2] addressed through img_idx (nullable).  Writes out[0..2] = {loss, ce, iou} (device),
 // dlogits (nullable), pred (nullable; (softmax > 0.5) as float).  extra_loss is added to the reported loss only (L2 term).
@@ -698,11 +500,9 @@ int mliis_softmax_ce(const float* logits, const float* labels, const int* img_id
                      hipStream_t stream) {
   MLIIS_REQUIRE(logits && labels && out && ws, MLIIS_ERR_ARG, "softmax_ce: null pointer");
   MLIIS_REQUIRE(N > 0 && H > 0 && W > 0, MLIIS_ERR_ARG, "softmax_ce: bad shape");
-  MLIIS_REQUIRE((reinterpret_cast<uintptr_t>(logits) & 7u) == 0 && (reinterpret_cast<uintptr_t>(labels) & 7u) == 0, MLIIS_ERR_ALIGN,
-                "softmax_ce: logits/labels must be 8-byte aligned");
+  MLIIS_REQUIRE(aligned8(logits) && aligned8(labels), MLIIS_ERR_ALIGN, "softmax_ce: logits/labels must be 8-byte aligned");
   const int HW = H * W;
-  int nblk = ceil_div((long long)HW, 256 * 8);
-  if (nblk > 256) nblk = 256;
+  const int nblk = part_blocks(HW);
   MLIIS_REQUIRE((size_t)N * nblk * 4 + 2 * (size_t)N <= ws_floats && aligned16(ws), MLIIS_ERR_WORKSPACE,
                 "softmax_ce: workspace too small or unaligned");
   float* coef = ws + (size_t)N * nblk * 4;
@@ -721,20 +521,11 @@ int mliis_softmax_ce(const float* logits, const float* labels, const int* img_id
   }
   return MLIIS_OK;
 }
-static inline int head_tiles(int n) { return (n + kHeadTile - 1) / kHeadTile; }
 // 1 when mliis_head_ce_fused takes this pair of maps (the image-side footprint of an 8 x 8 tile of the decoder's map fits its LDS
 // buffer: up-sampling factors up to ~4.5), else 0: use mliis_resize_bilinear_fwd -> mliis_softmax_ce -> mliis_resize_bilinear_bwd.
-int mliis_head_ce_fused_supported(int Hd, int Wd, int H, int W) {
-  if (Hd <= 1 || Wd <= 1 || H <= 1 || W <= 1) return 0;
-  const float sh = (float)(Hd - 1) / (float)(H - 1), sw = (float)(Wd - 1) / (float)(W - 1);
-  const int fh = (int)ceilf((float)(kHeadTile + 1) / sh) + 5, fw = (int)ceilf((float)(kHeadTile + 1) / sw) + 5;
-  return fh <= kHeadFoot && fw <= kHeadFoot;
-}
+int mliis_head_ce_fused_supported(int Hd, int Wd, int H, int W) { return head_fused_supported(Hd, Wd, H, W); }
 
-size_t mliis_head_ce_fused_workspace_floats(int N, int Hd, int Wd) {
-  if (N <= 0 || Hd <= 0 || Wd <= 0) return 0;
-  return (size_t)N * head_tiles(Hd) * head_tiles(Wd) * 4 + 2 * (size_t)N + 8;
-}
+size_t mliis_head_ce_fused_workspace_floats(int N, int Hd, int Wd) { return head_fused_workspace_floats(N, Hd, Wd); }
 
 // The training step's tail (no dice term) in two launches instead of five: small [N,Hd,Wd,2] = the final conv's output on the
 // decoder's map; logits = bilinear resize (align_corners) to [H,W]; softmax cross-entropy against labels [S,H,W,2] (addressed through
@@ -748,9 +539,7 @@ int mliis_head_ce_fused(const float* small, const float* labels, const int* img_
   MLIIS_REQUIRE(N > 0 && Hd > 1 && Wd > 1 && H > 1 && W > 1 && N <= 65535, MLIIS_ERR_ARG, "head_ce_fused: bad shape (both maps must be larger than 1x1)");
   MLIIS_REQUIRE(mliis_head_ce_fused_supported(Hd, Wd, H, W), MLIIS_ERR_UNSUPPORTED,
                 "head_ce_fused: up-sampling factor too large for the tile footprint (mliis_head_ce_fused_supported)");
-  MLIIS_REQUIRE((reinterpret_cast<uintptr_t>(small) & 7u) == 0 && (reinterpret_cast<uintptr_t>(labels) & 7u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dsmall) & 7u) == 0,
-                MLIIS_ERR_ALIGN, "head_ce_fused: tensors must be 8-byte aligned");
+  MLIIS_REQUIRE(aligned8(small) && aligned8(labels) && aligned8(dsmall), MLIIS_ERR_ALIGN, "head_ce_fused: tensors must be 8-byte aligned");
   const int tx = head_tiles(Wd), nblk = head_tiles(Hd) * tx;
   MLIIS_REQUIRE((size_t)N * nblk * 4 + 2 * (size_t)N <= ws_floats && aligned16(ws), MLIIS_ERR_WORKSPACE,
                 "head_ce_fused: workspace too small or unaligned");

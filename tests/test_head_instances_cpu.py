@@ -1,5 +1,6 @@
 """The decoder tail's routing mirror and case table (tests/head_instances.py) against the source they describe and the library's host-only
-queries, which answer without a GPU: the conditions and constants the mirror copies are still spelled that way in csrc/head.hip, the
+queries, which answer without a GPU: the conditions and constants the mirror copies are still spelled that way in csrc/head.hip and in
+csrc/loss_kernels.hpp (the loss kernels' geometry, fold and tiling, which head.hip shares with focal.hip), the
 kernels the source launches are the ones the cases reach, the workspace sizes and the fused head's predicate equal the library's over a
 grid of shapes, the footprint of every admitted pair of maps fits the fused head's LDS tile and covers every image row, and every case
 has the property it is there for."""
@@ -12,6 +13,7 @@ import pytest
 import head_instances as HI
 
 SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mliis_amd", "csrc", "head.hip")
+LOSS_HEADER = os.path.join(os.path.dirname(SOURCE), "loss_kernels.hpp")
 
 
 @pytest.fixture(scope="module")
@@ -30,9 +32,9 @@ def by_name():
 
 def test_the_source_still_routes_as_the_mirror_does():
     """The constants and conditions the mirror copies, as the source spells them."""
-    src = open(SOURCE).read()
-    for line in ("constexpr int kHeadTile = 8, kHeadFoot = 48;",
-                 "constexpr int kResizeRowsThreads = 512;",
+    head, loss = open(SOURCE).read(), open(LOSS_HEADER).read()
+    # what stays in head.hip is looked up there, what the loss kernels share with focal.hip in the header: a line in the wrong file fails
+    for line in ("constexpr int kResizeRowsThreads = 512;",
                  "if ((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0 && aligned16(x) && aligned16(y)) {",
                  "if ((C & 3) == 0 && (lddx & 3) == 0 && (lddy & 3) == 0 && aligned16(dx) && aligned16(dy)) {",
                  "if (C >= 16 && Wo <= 512 && Hi <= 65535 && N <= 65535) {",
@@ -40,30 +42,38 @@ def test_the_source_still_routes_as_the_mirror_does():
                  "if (2.f / sh + 3.f > 4.f)",
                  "const float sh = (float)(Hi - 1) / (float)(Ho - 1), sw = (float)(Wi - 1) / (float)(Wo - 1);",
                  "const bool merged = !dice && (dlogits || pred);",
-                 "int nblk = ceil_div((long long)HW, 256 * 8);",
-                 "if (nblk > 256) nblk = 256;",
-                 "return (size_t)N * nblk * 4 + 2 * (size_t)N + 8;",
-                 "return (size_t)N * head_tiles(Hd) * head_tiles(Wd) * 4 + 2 * (size_t)N + 8;",
                  "int nblk = (int)((per_img + 255) / 256);",
                  "if (nblk > 1024) nblk = 1024;",
                  "long long b = (q + 255) / 256;",
                  "if (b > 4096) b = 4096;",
+                 "const int tx = head_tiles(Wd), nblk = head_tiles(Hd) * tx;",
+                 "if (b > a || (b == a && ib < ia)) {"):
+        assert line in head and line not in loss, line
+    for line in ("constexpr int kHeadTile = 8, kHeadFoot = 48;",
+                 "constexpr int kPartPixels = 256 * 8;",
+                 "constexpr int kPartMaxBlocks = 256;",
+                 "int nblk = ceil_div(HW, kPartPixels);",
+                 "if (nblk > kPartMaxBlocks) nblk = kPartMaxBlocks;",
+                 "return (size_t)N * nblk * 4 + 2 * (size_t)N + 8;",
+                 "return (size_t)N * head_tiles(Hd) * head_tiles(Wd) * 4 + 2 * (size_t)N + 8;",
                  "for (int n0 = 0; n0 < N; n0 += 8) {",
                  "for (int b = lane; b < nblk; b += 32) {",
                  "const int v = (int)floorf((float)(i - 1) / s) - 1;",
                  "const int v = (int)ceilf((float)(i + 1) / s) + 1;",
                  "const int fh = (int)ceilf((float)(kHeadTile + 1) / sh) + 5, fw = (int)ceilf((float)(kHeadTile + 1) / sw) + 5;",
                  "return fh <= kHeadFoot && fw <= kHeadFoot;",
-                 "static inline int head_tiles(int n) { return (n + kHeadTile - 1) / kHeadTile; }",
-                 "const int tx = head_tiles(Wd), nblk = head_tiles(Hd) * tx;",
-                 "if (b > a || (b == a && ib < ia)) {"):
-        assert line in src, line
-    assert src.count("if (nblk > 256) nblk = 256;") == 2 and "int nblk = ceil_div((long long)H * W, 256 * 8);" in src       # launch and workspace query
+                 "static inline int head_tiles(int n) { return (n + kHeadTile - 1) / kHeadTile; }"):
+        assert loss.count(line) == 1 and line not in head, line
+    # launch and workspace query count the partial blocks with the one part_blocks(); the geometry has one definition, in the header
+    assert "const int nblk = part_blocks(HW);" in head and "const int nblk = part_blocks((long long)H * W);" in loss
+    assert "size_t mliis_softmax_ce_workspace_floats(int N, int H, int W) { return loss_workspace_floats(N, H, W); }" in head
+    for name in ("kHeadTile =", "kHeadFoot =", "int head_lo(", "int head_hi(", "int head_tiles(", "int head_fused_supported(", "void loss_fold("):
+        assert (head.count(name), loss.count(name)) == (0, 1), name
     # the resize transposes spell the candidate range as head_lo / head_hi do
-    assert src.count("(int)floorf((float)(hi - 1) / sh) - 1, ho_hi = (int)ceilf((float)(hi + 1) / sh) + 1;") == 2
-    assert src.count("(int)floorf((float)(wi - 1) / sw) - 1, wo_hi = (int)ceilf((float)(wi + 1) / sw) + 1;") == 2
+    assert head.count("(int)floorf((float)(hi - 1) / sh) - 1, ho_hi = (int)ceilf((float)(hi + 1) / sh) + 1;") == 2
+    assert head.count("(int)floorf((float)(wi - 1) / sw) - 1, wo_hi = (int)ceilf((float)(wi + 1) / sw) + 1;") == 2
     # the swish-mask launches spell ew_blocks' cap inline
-    assert src.count("(q + 255) / 256 > 4096 ? 4096 : (q + 255) / 256") == 2
+    assert head.count("(q + 255) / 256 > 4096 ? 4096 : (q + 255) / 256") == 2
     assert (HI.EW_MAX_BLOCKS, HI.CE_PIXELS_PER_BLOCK, HI.CE_MAX_BLOCKS, HI.CE_FOLD_IMAGES, HI.CE_FOLD_LANES) == (4096, 2048, 256, 8, 32)
     assert (HI.DARC1_MAX_BLOCKS, HI.HEAD_TILE, HI.HEAD_FOOT, HI.ROWS_MIN_C, HI.ROWS_MAX_WO, HI.ROWS_THREADS) == (1024, 8, 48, 16, 512, 512)
 

@@ -8,7 +8,7 @@ all; host clock around --steps meta-steps that end in a device synchronise, afte
 time limit (SIGALRM with the default action: a repeat that exceeds --limit seconds ends the process instead of hanging it).
 
     python tools/bench_focal.py [--steps 100] [--warmup 5] [--repeats 3] [--limit 120] [--tree DIR] [--json out.json]
-    python tools/bench_focal.py --parent DIR --md profiles/focal.md [...]
+    python tools/bench_focal.py --parent DIR --md profiles/focal.md [--title "..."] [...]
 
 --tree DIR imports mliis_amd from another checkout (the same tool on the parent commit: a Learner that does not know focal_gamma is timed
 in the setting it has).  --parent DIR (a built checkout of the parent commit) makes this process an orchestrator that never touches the GPU
@@ -124,25 +124,30 @@ def orchestrate(a):
     (_, p1), (_, t), (_, p2) = runs
     per_step = t["images_per_step"]
     ms = lambda r, k: 1e3 * per_step / r["images_per_s"][k]["median"]   # noqa: E731  (ms per inner step)
-    lines = ["# What the focal, foreground-weighted pixel loss costs", "",
+    lines = ["# " + a.title, "",
              "One MI355X, `tools/bench_focal.py`: config 2 of `BASELINE.json` (EfficientLab-6-3, 224², meta-batch 1, 5 shots, 8 inner SGD steps of",
              "batch 8, fp32, captured graphs), inner-loop images/s of `Gecko.train_step`. Host clock around {} meta-steps that end in a device".format(t["steps"]),
              "synchronise, after {} untimed ones; every setting {} times, the settings alternating. Three processes, one after the other: the".format(t["warmup"], t["repeats"]),
-             "parent commit, this tree, the parent commit again (the parent commit has no `focal` setting).", "",
-             "    python tools/bench_focal.py --parent <built checkout of the parent commit> --md profiles/focal.md --steps {} --warmup {} --repeats {}".format(
-                 t["steps"], t["warmup"], t["repeats"]), "",
+             "parent commit, this tree, the parent commit again{}.".format(
+                 "" if all("focal" in r["images_per_s"] for r in (p1, p2)) else " (the parent commit has no `focal` setting)"), "",
+             "    python tools/bench_focal.py --parent <built checkout of the parent commit> --md {} --steps {} --warmup {} --repeats {}".format(
+                 os.path.relpath(os.path.abspath(a.md), here), t["steps"], t["warmup"], t["repeats"]), "",
              "`--focal-gamma {} --fg-weight {}`.".format(t["gamma"], t["fg_weight"]), "",
              "| setting | this tree: median (min-max) images/s | parent, process 1 | parent, process 2 |", "|---|---|---|---|"]
     for name in SETTINGS:
         lines.append("| `{}` | {} | {} | {} |".format(name, _cell(t, name), _cell(p1, name), _cell(p2, name)))
-    off, a1, a2 = t["images_per_s"]["without_flags"], p1["images_per_s"]["without_flags"], p2["images_per_s"]["without_flags"]
-    lo, hi = min(a1["min"], a2["min"]), max(a1["max"], a2["max"])
-    inside = lo <= off["median"] <= hi
-    lines += ["", "* **Flags off**: {:.1f} images/s (median) against {:.1f}-{:.1f} over the two processes of the parent commit (medians {:.1f} and {:.1f}): {}.".format(
-        off["median"], lo, hi, a1["median"], a2["median"],
-        "inside the spread between the two" if inside else "OUTSIDE the spread between the two ({:+.2f} % against their mean)".format(
-            100 * (off["median"] / ((a1["median"] + a2["median"]) / 2) - 1)))]
-    on = t["images_per_s"]["focal"]
+    lines.append("")
+    for name, title in (("without_flags", "Flags off"), ("focal", "With the flags, against the parent commit")):
+        if not all(name in r["images_per_s"] for r in (p1, p2)):      # (a parent commit from before the option)
+            continue
+        off, a1, a2 = t["images_per_s"][name], p1["images_per_s"][name], p2["images_per_s"][name]
+        lo, hi = min(a1["min"], a2["min"]), max(a1["max"], a2["max"])
+        inside = lo <= off["median"] <= hi
+        lines += ["* **{}**: {:.1f} images/s (median) against {:.1f}-{:.1f} over the two processes of the parent commit (medians {:.1f} and {:.1f}): {}.".format(
+            title, off["median"], lo, hi, a1["median"], a2["median"],
+            "inside the spread between the two" if inside else "OUTSIDE the spread between the two ({:+.2f} % against their mean)".format(
+                100 * (off["median"] / ((a1["median"] + a2["median"]) / 2) - 1)))]
+    off, on = t["images_per_s"]["without_flags"], t["images_per_s"]["focal"]
     lines += ["* **With the flags** (the focal head and its own fold launch in place of the fused head whose fold rides in the next launch), per",
               "  8-image inner step against `without_flags` of the same process: {:.1f} images/s, {:+.1f} µs on {:.3f} ms ({:+.2f} %).  No target is set.".format(
                   on["median"], 1e3 * (ms(t, "focal") - ms(t, "without_flags")), ms(t, "without_flags"), 100 * (on["median"] / off["median"] - 1)),
@@ -170,6 +175,7 @@ def main(argv=None):
     p.add_argument("--json", default=None)
     p.add_argument("--parent", default=None, help="built checkout of the parent commit: run it, this tree and it again in child processes")
     p.add_argument("--md", default=None, help="with --parent: the markdown file the table goes to")
+    p.add_argument("--title", default="What the focal, foreground-weighted pixel loss costs", help="with --md: the file's heading")
     a = p.parse_args(argv)
     if a.parent:
         if not a.md:
