@@ -222,6 +222,15 @@ _EXT = [
                                         "validation tasks and add selected_on_val = {threshold, val_iou, test_iou_at_threshold} to the file: "
                                         "the threshold chosen on tasks the test score never saw.  Needs --num_val_tasks > 0; not with "
                                         "--eval_val_tasks")),
+    ("--eval-tta", dict(nargs="+", choices=["hflip", "vflip", "hvflip"], default=None, metavar="VIEW",
+                        help="flip test-time augmentation in the final evaluation passes (the train-task pass, the meta-test / meta-val "
+                             "pass and the validation pass of --threshold-sweep-val): every test batch is also predicted mirrored -- hflip: "
+                             "columns, vflip: rows, hvflip: both; one more forward pass per view -- each view's decoder-resolution LOGITS "
+                             "are mirrored back and averaged with the plain view's on the device (csrc/tta.hip) before anything scores "
+                             "them, so the printed IoUs, meta-test_results.json, saved masks and the threshold sweep are those of the "
+                             "merged prediction on every scoring path alike.  Averaging logits is a geometric mean of the views' odds, not "
+                             "a mean of probabilities.  Not applied to early stopping, the update-hyperparameter search, the k-shot curves "
+                             "or meta-training")),
 ]
 
 
@@ -258,6 +267,13 @@ def threshold_sweep(a):
     if on_val and getattr(a, "eval_val_tasks", False):
         raise ValueError("--threshold-sweep-val with --eval_val_tasks would select and report on the same tasks: use --threshold-sweep alone")
     return sweep, on_val
+
+
+def eval_views(a) -> tuple:
+    """The canonical view tuple of --eval-tta (views.canonical: hflip, vflip, hvflip in that order whatever order was given; a repeat is
+    refused), () without the flag.  Kept out of evaluate_kwargs like the prediction writer: only the final evaluation passes merge views."""
+    from .views import canonical
+    return canonical(getattr(a, "eval_tta", None) or ())
 
 
 def argument_parser(extensions: bool = True) -> argparse.ArgumentParser:

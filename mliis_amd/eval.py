@@ -18,7 +18,7 @@ def evaluate_gecko(learner, dataset, num_classes=1, num_shots=5, eval_inner_batc
                    num_samples=100, transductive=False, weight_decay_rate=1, meta_fn=Gecko, visualize_predicted_segmentations=False,
                    save_fine_tuned_checkpoints=False, save_fine_tuned_checkpoints_dir: Optional[str] = None, lr_scheduler=None, lr=None,
                    augment=False, serially_eval_all_tasks: bool = False, aug_rate: Optional[float] = None, aug_pool=None,
-                   lanes=(), device_metrics: bool = False, prediction_writer=None, threshold_sweep=None,
+                   lanes=(), device_metrics: bool = False, prediction_writer=None, threshold_sweep=None, eval_views=(),
                    **_ignored) -> Tuple[float, Dict[str, List[float]]]:
     print("Evaluating with eval_inner_iters: {}".format(eval_inner_iters))
     print("Evaluating with lr: {}".format(lr))
@@ -26,7 +26,8 @@ def evaluate_gecko(learner, dataset, num_classes=1, num_shots=5, eval_inner_batc
     gecko = meta_fn(learner, transductive=transductive, pre_step_op=pre_step_op, lr_scheduler=lr_scheduler, augment=augment,
                     aug_rate=aug_rate, rng_mode="reference", dist=_Single(), aug_pool=aug_pool, lanes=lanes, **_device_metrics_kw(device_metrics),
                     **({"prediction_writer": prediction_writer} if prediction_writer is not None else {}),   # (only this driver saves predictions)
-                    **({"threshold_sweep": threshold_sweep} if threshold_sweep is not None else {}))   # (... and sweeps the threshold)
+                    **({"threshold_sweep": threshold_sweep} if threshold_sweep is not None else {}),   # (... and sweeps the threshold)
+                    **({"eval_views": tuple(eval_views)} if eval_views else {}))   # (... and merges mirrored views: --eval-tta)
     mean_ious, task_iou_map = [], {}
     for i in range(num_samples):
         if threshold_sweep is not None and callable(getattr(threshold_sweep, "begin_pass", None)):

@@ -39,6 +39,7 @@ from .passes import _Passes
 from .plan import _Plan, layer_names
 from .steplog import MIN_CAPACITY as MIN_LOG_CAPACITY
 from .steplog import decode as decode_step_log
+from .views import canonical as canonical_views
 
 
 def _queue_ring_fetch(pin, ring, cursor):
@@ -853,15 +854,41 @@ class Learner(_Passes):
         return False
 
     # ------------------------------------------------------------------------------------------- inference
-    def predict(self, images, training: bool = False, return_logits: bool = False):
+    def _forward_views(self, P: _Plan, x, idx, training: bool, views):
+        """Flip test-time augmentation (views: a canonical, non-empty tuple of views.VIEWS): P.small = the mean of the decoder-resolution
+        logits of the batch and of its mirrored views, each view's logits mirrored back,
+            merged = (z_id + (F_v1(z_v1) + F_v2(z_v2) + ...)) * fl32(1 / (K + 1))          fp32, every sum and the product rounded once.
+        Per view: ops.view_gather mirrors the whole batch into P.view_x, one more forward pass of the same mode runs on it, ops.view_merge
+        mirrors its logits back into the running sum P.view_acc (the first view is stored as it is, not added to zero); then the identity
+        pass exactly as without views, and one in-place merge into P.small.  Flips commute with the align-corners resize, so everything
+        downstream reads P.small as always.  Logits are averaged, not probabilities.  Call on the learner's stream."""
+        H, hd = self.arch.image_size, self.arch.h_dec
+        if P.view_x is None:
+            P.view_x = torch.zeros((P.N, H, H, 3), dtype=torch.float32, device=self.device)
+            P.view_acc = torch.zeros((P.N, hd, hd, 2), dtype=torch.float32, device=self.device)
+        for k, v in enumerate(views):
+            ops.view_gather(x, idx, v, out=P.view_x)
+            self._forward(P, P.view_x, None, training, upsample=False, stochastic=False)
+            ops.view_merge(P.view_acc, P.view_acc if k else None, P.small, v, 1.0)
+        self._forward(P, x, idx, training, upsample=False, stochastic=False)
+        ops.view_merge(P.small, P.small, P.view_acc, (False, False), 1.0 / (len(views) + 1))
+
+    def predict(self, images, training: bool = False, return_logits: bool = False, views=()):
         """predictions tensor of the reference: (softmax(logits) > 0.5) as float, [N,H,W,2].  training=True: batch statistics in every
-        batch norm; the stochastic sites (drop-connect, final-layer and ASPP dropout) stay off -- their masks belong to a training step."""
+        batch norm; the stochastic sites (drop-connect, final-layer and ASPP dropout) stay off -- their masks belong to a training step.
+        views: flip test-time augmentation (_forward_views); () = off, the launches of a call without the keyword."""
+        views = canonical_views(views)
         images = torch.as_tensor(images)
         N = images.shape[0]
         P = self._plan(N, infer=True)
         with torch.cuda.stream(self.stream):
             x = images.to(device=self.device, dtype=torch.float32).contiguous()
-            logits = self._forward(P, x, None, training, stochastic=False)
+            if views:
+                self._forward_views(P, x, None, training, views)
+                H = self.arch.image_size
+                logits = ops.resize_bilinear_fwd(P.small, (H, H), out=P.logits)
+            else:
+                logits = self._forward(P, x, None, training, stochastic=False)
             dummy = torch.zeros_like(logits)
             ops.softmax_ce(logits, dummy, None, 0.0, False, 0.0, want_grad=False, want_pred=True, pred=P.pred, out=P.loss_out, ws=self.ws)
             out = P.pred.clone()
@@ -869,17 +896,20 @@ class Learner(_Passes):
         self.stream.synchronize()
         return (out, lg) if return_logits else out
 
-    def predict_resident(self, idx: Sequence[int], training: bool = False):
+    def predict_resident(self, idx: Sequence[int], training: bool = False, views=()):
         """predict() on images `idx` of the task made resident by load_task()."""
+        views = canonical_views(views)
         with torch.cuda.stream(self.stream):
             x = self.shots_x[torch.tensor(list(idx), dtype=torch.long, device=self.device)]
-        return self.predict(x, training=training)
+        return self.predict(x, training=training, views=views) if views else self.predict(x, training=training)
 
-    def score_resident(self, idx: Sequence[int], training: bool = False) -> np.ndarray:
+    def score_resident(self, idx: Sequence[int], training: bool = False, views=()) -> np.ndarray:
         """The score of predict_resident(idx) against the resident labels without its mask: int64 [len(idx), 4] =
         {|P & L|, |P | L|, |P|, |L|} per image (ops.mask_iou_counts; metrics.iou_from_counts(row[0], row[1]) is metrics.iou of that
         image's prediction).  The images are read through the index vector and the decoder-resolution logits are scored in place: no
-        gather, no resize launch, no full-resolution tensor, 16 bytes per image back to the host."""
+        gather, no resize launch, no full-resolution tensor, 16 bytes per image back to the host.  views: flip test-time augmentation
+        (_forward_views: the counts are those of the merged logits); () = off, the launches of a call without the keyword."""
+        views = canonical_views(views)
         idx = [int(i) for i in idx]
         N = len(idx)
         if N == 0:
@@ -894,18 +924,22 @@ class Learner(_Passes):
                 P.counts = torch.zeros((N, 4), dtype=torch.int32, device=self.device)
                 P.counts_pin = torch.zeros((N, 4), dtype=torch.int32).pin_memory()
             self._upload_idx(P, idx)
-            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            if views:
+                self._forward_views(P, self.shots_x, P.idx, training, views)
+            else:
+                self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
             ops.mask_iou_counts(P.small, self.shots_y, P.idx, (H, H), counts=P.counts)
             P.counts_pin.copy_(P.counts, non_blocking=True)
         self.stream.synchronize()
         return P.counts_pin.numpy().astype(np.int64)
 
-    def mask_resident(self, idx: Sequence[int], training: bool = False, counts: bool = False, last_only: bool = False):
+    def mask_resident(self, idx: Sequence[int], training: bool = False, counts: bool = False, last_only: bool = False, views=()):
         """The prediction masks of predict_resident(idx) -- bool [len(idx), H, W], = predict_resident(idx)[..., 1] > 0.5 -- read back as one
         bit per pixel (ops.mask_pack on the decoder-resolution logits of score_resident's forward pass; metrics.unpack_mask on the host):
         H W / 8 bytes per image instead of the 8 H W of the fp32 prediction tensor.  counts=True: (masks, int64 [len(idx), 4]), the rows of
         score_resident from the same launch.  last_only=True: only the last image of the batch is packed and returned ([1,H,W] / [1,4]) --
-        the per-sample evaluation's "train images + one test image, keep the last"."""
+        the per-sample evaluation's "train images + one test image, keep the last".  views: as in score_resident."""
+        views = canonical_views(views)
         idx = [int(i) for i in idx]
         N = len(idx)
         if N == 0:
@@ -925,7 +959,10 @@ class Learner(_Passes):
                 P.counts = torch.zeros((N, 4), dtype=torch.int32, device=self.device)
                 P.counts_pin = torch.zeros((N, 4), dtype=torch.int32).pin_memory()
             self._upload_idx(P, idx)
-            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            if views:
+                self._forward_views(P, self.shots_x, P.idx, training, views)
+            else:
+                self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
             if counts:
                 ops.mask_pack(P.small[n0:], (H, H), self.shots_y, P.idx[n0:], bits=P.bits[n0:], counts=P.counts[n0:])
                 P.counts_pin[n0:].copy_(P.counts[n0:], non_blocking=True)
@@ -936,12 +973,13 @@ class Learner(_Passes):
         masks = unpack_mask(P.bits_pin[n0:].numpy(), H, H)
         return (masks, P.counts_pin[n0:].numpy().astype(np.int64)) if counts else masks
 
-    def histogram_resident(self, idx: Sequence[int], training: bool = False, last_only: bool = False, masks: bool = False):
+    def histogram_resident(self, idx: Sequence[int], training: bool = False, last_only: bool = False, masks: bool = False, views=()):
         """The threshold sweep's view of predict_resident(idx): int64 [n, 2, 256], per image the histogram of its channel-1 probability
         split by label class (ops.prob_histogram on the decoder-resolution logits of score_resident's forward pass: 2 KB per image come
         back).  metrics.counts_from_histogram(...)[..., 128, :] are score_resident's rows bit for bit; the other rows are the counts at the
         other thresholds k/256.  last_only=True: only the last image of the batch ([1,2,256]), as in mask_resident.  masks=True:
-        (hist, bool [n,H,W]) -- mask_resident's masks packed from the same logits, no second forward pass."""
+        (hist, bool [n,H,W]) -- mask_resident's masks packed from the same logits, no second forward pass.  views: as in score_resident."""
+        views = canonical_views(views)
         idx = [int(i) for i in idx]
         N = len(idx)
         if N == 0:
@@ -962,7 +1000,10 @@ class Learner(_Passes):
                 P.bits = torch.zeros((N, words), dtype=torch.int64, device=self.device)
                 P.bits_pin = torch.zeros((N, words), dtype=torch.int64).pin_memory()
             self._upload_idx(P, idx)
-            self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
+            if views:
+                self._forward_views(P, self.shots_x, P.idx, training, views)
+            else:
+                self._forward(P, self.shots_x, P.idx, training, upsample=False, stochastic=False)
             ops.prob_histogram(P.small[n0:], (H, H), self.shots_y, P.idx[n0:], hist=P.hist[n0:])
             P.hist_pin[n0:].copy_(P.hist[n0:], non_blocking=True)
             if masks:

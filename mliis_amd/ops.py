@@ -17,7 +17,7 @@ import torch
 
 from . import clip as _clip
 from . import layerlog as _layerlog
-from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib
+from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib, tta_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1407,6 +1407,65 @@ def prob_histogram(small, size, labels, idx=None, hist=None):
     _timed("prob_histogram", {}, lambda: sweep_lib.call("mliis_prob_histogram", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd, H, W,
                                                         C.c_void_p(hist.data_ptr()), _stream()))
     return hist
+
+
+def _flip_pair(flips, what):
+    """(flip_rows, flip_cols) as ints from a pair of truth values or a view name of mliis_amd.views."""
+    if isinstance(flips, str):
+        from .views import FLIPS
+        if flips not in FLIPS:
+            raise MliisError("{}: unknown view {!r}".format(what, flips))
+        flips = FLIPS[flips]
+    try:
+        fr, fc = flips
+    except (TypeError, ValueError):
+        raise MliisError("{}: flips must be (flip_rows, flip_cols) or a view name, got {!r}".format(what, flips))
+    return int(bool(fr)), int(bool(fc))
+
+
+def view_gather(src, idx, flips, out=None):
+    """out [N,H,W,C] = images idx (device int32 [N]; None = rows 0..N-1 of src, N = src.shape[0]) of src [S,H,W,C], mirrored: flips =
+    (flip_rows, flip_cols) or a view name (views.FLIPS; hflip mirrors the columns like np.fliplr).  The words are copied bit for bit, every
+    element of out is written once and src is only read; with no flip it is a plain gather.  1 <= C <= 4; out must not overlap src.
+    libmliis_tta.so (include/mliis_tta.h, csrc/tta.hip), loaded at the first call."""
+    fr, fc = _flip_pair(flips, "view_gather")
+    _dense(src, idx, out)
+    if src.dim() != 4 or not 1 <= src.shape[-1] <= 4:
+        raise MliisError("view_gather: expected src [S,H,W,C] with 1 <= C <= 4, got {}".format(tuple(src.shape)))
+    S, H, W, Cn = src.shape
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or idx.numel() < 1 or idx.device != src.device):
+        raise MliisError("view_gather: idx must be a device int32 vector of image indices on src's device")
+    N = S if idx is None else idx.numel()
+    if N < 1 or H < 1 or W < 1:
+        raise MliisError("view_gather: empty tensor {}".format(tuple(src.shape)))
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (N, H, W, Cn) or out.device != src.device):
+        raise MliisError("view_gather out: expected a float32 tensor of shape {} on src's device, got {} {}".format((N, H, W, Cn), tuple(out.shape),
+                                                                                                            out.dtype))
+    out = torch.empty((N, H, W, Cn), dtype=torch.float32, device=src.device) if out is None else out
+    _timed("view_gather", {}, lambda: tta_lib.call("mliis_view_gather", _ptr(_chk(src)), _ptr(idx), N, H, W, Cn, fr, fc, _ptr(_chk(out)), _stream()))
+    return out
+
+
+def view_merge(dst, a, b, flips, scale):
+    """dst [N,Hd,Wd,C] = (a + b mirrored by flips) * scale, fp32, the sum and the product rounded once each; a = None: dst = b mirrored *
+    scale, no addition.  dst may be a (in place); dst must not be b.  scale: finite and positive.  Returns dst.  libmliis_tta.so
+    (include/mliis_tta.h, csrc/tta.hip), loaded at the first call."""
+    fr, fc = _flip_pair(flips, "view_merge")
+    _dense(dst, a, b)
+    if dst.dim() != 4 or not 1 <= dst.shape[-1] <= 4 or dst.numel() == 0:
+        raise MliisError("view_merge: expected dst [N,Hd,Wd,C] with 1 <= C <= 4, got {}".format(tuple(dst.shape)))
+    for name, t in (("a", a), ("b", b)):
+        if t is not None and (tuple(t.shape) != tuple(dst.shape) or t.device != dst.device):
+            raise MliisError("view_merge {}: expected shape {} on dst's device, got {}".format(name, tuple(dst.shape), tuple(t.shape)))
+    if b is None:
+        raise MliisError("view_merge: b is required")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise MliisError("view_merge: scale must be finite and positive, got {}".format(scale))
+    N, Hd, Wd, Cn = dst.shape
+    _timed("view_merge", {}, lambda: tta_lib.call("mliis_view_merge", _ptr(_chk(dst)), _ptr(_chk(a)) if a is not None else None, _ptr(_chk(b)),
+                                                  N, Hd, Wd, Cn, fr, fc, scale, _stream()))
+    return dst
 
 
 def task_expand_u8(images_u8, masks_u8, src_idx, x, y):

@@ -339,6 +339,9 @@ class _Plan:
         # Learner.histogram_resident: the [N,2,256] probability histograms on the device and their pinned host copy (allocated by its
         # first call; with masks=True it packs into the buffers above)
         self.hist = self.hist_pin = None
+        # Learner._forward_views (views= of the scoring calls): the mirrored batch [N,H,H,3] and the sum of the mirrored views'
+        # decoder-resolution logits [N,hd,hd,2] (allocated by the first call with a view; never without one)
+        self.view_x = self.view_acc = None
 
     @property
     def graph(self):

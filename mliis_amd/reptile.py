@@ -125,8 +125,15 @@ class Gecko:
     def __init__(self, learner, variables=None, transductive: bool = False, pre_step_op=None, lr_scheduler=None, augment: bool = False,
                  aug_rate: Optional[float] = None, dist: Optional[Dist] = None, rng_mode: Optional[str] = None, seed: int = 0,
                  aug_pool=None, lanes: Sequence = (), device_metrics: bool = False, prediction_writer=None, step_log: bool = False,
-                 on_divergence: str = "off", layer_log: bool = False, layer_log_interval: int = 100, threshold_sweep=None):
+                 on_divergence: str = "off", layer_log: bool = False, layer_log_interval: int = 100, threshold_sweep=None, eval_views=()):
         self.learner = learner
+        # eval_views: flip test-time augmentation at evaluation (views.VIEWS, canonical order whatever order is given).  evaluate()'s
+        # scoring sites -- _test_predictions, _device_ious, _ious_saving, _ious_sweeping, on the learner and the lanes -- pass views= to
+        # the learner, which predicts each mirrored view as well and merges the decoder-resolution logits (Learner._forward_views); early
+        # stopping, the k-shot curves and so the hyperparameter search never do.  Opt-in: () passes no keyword at all.
+        from .views import canonical, require_views_support
+        self.eval_views = canonical(eval_views)
+        require_views_support([learner] + list(lanes), self.eval_views)
         # threshold_sweep: a sink -- callable(task name, per-image IoU curves [n, 256], per-image histograms [n, 2, 256]), e.g.
         # metrics.ThresholdSweep.  evaluate()'s tasks then score from Learner.histogram_resident: per test image a 2 x 256 histogram of its
         # foreground probability by label class comes back (ops.prob_histogram) in place of score_resident's four counts, the IoUs are
@@ -632,7 +639,8 @@ class Gecko:
             iou = self._evaluate(train_idx, test_idx, labels, inner_batch_size, inner_iters, replacement, lr=lr, task_name=name,
                                  save_fine_tuned_checkpoints=save_fine_tuned_checkpoints,
                                  save_fine_tuned_checkpoints_dir=save_fine_tuned_checkpoints_dir, eval_sample_num=eval_sample_num,
-                                 aug_rate=self.aug_rate if aug_rate is None else aug_rate, images=images, drop_rate=drop_rate)
+                                 aug_rate=self.aug_rate if aug_rate is None else aug_rate, images=images, drop_rate=drop_rate,
+                                 **({"views": self.eval_views} if self.eval_views else {}))
             ious.append(iou)
             task_iou_map[name] = iou
         mean_iou = float(np.nanmean(ious))
@@ -677,13 +685,14 @@ class Gecko:
                         self._fine_tune_step(idx, j, lr, self.lr_scheduler, drop_rate, lane)
             for lane, name, images, labels, train_idx, test_idx, _ in group:
                 if self.threshold_sweep is not None:
-                    class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, name, eval_sample_num, images, lane)))
+                    class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, name, eval_sample_num, images, lane, self.eval_views)))
                 elif self.prediction_writer is not None:
-                    class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, name, eval_sample_num, images, lane)))
+                    class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, name, eval_sample_num, images, lane,
+                                                                        self.eval_views)))
                 elif self.device_metrics:
-                    class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane)))
+                    class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, lane, self.eval_views)))
                 else:
-                    preds = self._test_predictions(train_idx, test_idx, lane)
+                    preds = self._test_predictions(train_idx, test_idx, lane, self.eval_views)
                     lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
                     class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
                 print("Mean task IoU: {}".format(class_iou))
@@ -706,8 +715,9 @@ class Gecko:
 
     def _evaluate(self, train_idx, test_idx, labels, inner_batch_size, inner_iters, replacement, lr=None, task_name=None,
                   save_fine_tuned_checkpoints=False, save_fine_tuned_checkpoints_dir=None, eval_sample_num=None, aug_rate=None,
-                  images=None, drop_rate=None):
-        """Evaluates a single task's train/test split (reptile.py:235-294): ALL global variables are restored afterwards."""
+                  images=None, drop_rate=None, views=()):
+        """Evaluates a single task's train/test split (reptile.py:235-294): ALL global variables are restored afterwards.  views:
+        evaluate() passes its eval_views; the k-shot curves and the early-stopping re-evaluation call without them."""
         import numpy as np
         from .metrics import iou as _iou
         L = self.learner
@@ -742,13 +752,15 @@ class Gecko:
         if self.augmenter is not None and not self.device_aug:
             L.load_task(images, labels)   # the augmented batches replaced the resident task
         if self.threshold_sweep is not None:
-            class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, task_name, eval_sample_num, images)))
+            class_iou = float(np.nanmean(self._ious_sweeping(train_idx, test_idx, task_name, eval_sample_num, images,
+                                                                  views=views)))
         elif self.prediction_writer is not None:
-            class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, task_name, eval_sample_num, images)))
+            class_iou = float(np.nanmean(self._ious_saving(train_idx, test_idx, labels, task_name, eval_sample_num, images,
+                                                                views=views)))
         elif self.device_metrics:
-            class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx)))
+            class_iou = float(np.nanmean(self._device_ious(train_idx, test_idx, views=views)))
         else:
-            preds = self._test_predictions(train_idx, test_idx)
+            preds = self._test_predictions(train_idx, test_idx, views=views)
             lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
             class_iou = float(np.nanmean([_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]))
         print("Mean task IoU: {}".format(class_iou))
@@ -899,30 +911,33 @@ class Gecko:
                 ks.extend(k_range)
         return ks, results
 
-    def _test_predictions(self, train_idx, test_idx, L=None):
+    def _test_predictions(self, train_idx, test_idx, L=None, views=()):
         """reptile.py:482-524: transductive -> all test images in one inference-mode batch; otherwise one call per test image on the
-        batch [train images..., that test image], keeping the last prediction."""
+        batch [train images..., that test image], keeping the last prediction.  views: evaluate()'s eval_views (the keyword is passed to
+        the learner only when set, here and in the three helpers below)."""
         L = L or self.learner
+        kw = {"views": views} if views else {}
         if self._transductive:
-            return L.predict_resident(list(test_idx), training=False).cpu().numpy()
+            return L.predict_resident(list(test_idx), training=False, **kw).cpu().numpy()
         out = []
         for t in test_idx:
-            out.append(L.predict_resident(list(train_idx) + [t], training=False)[-1].cpu().numpy())
+            out.append(L.predict_resident(list(train_idx) + [t], training=False, **kw)[-1].cpu().numpy())
         return out
 
-    def _device_ious(self, train_idx, test_idx, L=None) -> List[float]:
+    def _device_ious(self, train_idx, test_idx, L=None, views=()) -> List[float]:
         """device_metrics: the per-image IoUs of _test_predictions + metrics.iou from the device's counts, over the same batches --
         transductive: one batch of all test images; otherwise one batch [train images..., that test image] per test image, its last
         row kept."""
         from .metrics import iou_from_counts
         L = L or self.learner
+        kw = {"views": views} if views else {}
         if self._transductive:
-            rows = L.score_resident(list(test_idx), training=False)
+            rows = L.score_resident(list(test_idx), training=False, **kw)
         else:
-            rows = [L.score_resident(list(train_idx) + [t], training=False)[-1] for t in test_idx]
+            rows = [L.score_resident(list(train_idx) + [t], training=False, **kw)[-1] for t in test_idx]
         return [iou_from_counts(r[0], r[1]) for r in rows]
 
-    def _ious_sweeping(self, train_idx, test_idx, task_name, eval_sample_num=None, images=None, L=None) -> List[float]:
+    def _ious_sweeping(self, train_idx, test_idx, task_name, eval_sample_num=None, images=None, L=None, views=()) -> List[float]:
         """threshold_sweep: _device_ious' per-image IoUs from the k = 128 row of the device's histograms, over the same batches (one
         histogram_resident call in place of each score_resident call), while the sink receives the task's per-image curves and
         histograms; with a prediction writer each image's mask comes back from the same call and is saved as _ious_saving saves it."""
@@ -930,14 +945,15 @@ class Gecko:
         from .metrics import counts_from_histogram, iou_curve, iou_from_counts
         L = L or self.learner
         W = self.prediction_writer
+        kw = {"views": views} if views else {}
         masks = None
         if self._transductive:
-            got = L.histogram_resident(list(test_idx), training=False, masks=W is not None)
+            got = L.histogram_resident(list(test_idx), training=False, masks=W is not None, **kw)
             hists, masks = got if W is not None else (got, None)
         else:
             hists, masks = [], []
             for t in test_idx:
-                got = L.histogram_resident(list(train_idx) + [t], training=False, last_only=True, masks=W is not None)
+                got = L.histogram_resident(list(train_idx) + [t], training=False, last_only=True, masks=W is not None, **kw)
                 h, m = got if W is not None else (got, None)
                 hists.append(h[-1])
                 if W is not None:
@@ -951,7 +967,7 @@ class Gecko:
         half = hists.shape[-1] // 2
         return [iou_from_counts(r[0], r[1]) for r in counts_from_histogram(hists)[:, half]]
 
-    def _ious_saving(self, train_idx, test_idx, labels, task_name, eval_sample_num, images=None, L=None) -> List[float]:
+    def _ious_saving(self, train_idx, test_idx, labels, task_name, eval_sample_num, images=None, L=None, views=()) -> List[float]:
         """The per-image IoUs of a task's test images -- _device_ious' with device_metrics, _test_predictions + metrics.iou otherwise, over
         the same batches and to the same floats -- while the prediction writer saves each image's mask: with device_metrics the mask
         packed by the launch that counts (one mask_resident call in place of each score_resident call), otherwise the channel-1 plane
@@ -959,18 +975,19 @@ class Gecko:
         import numpy as np
         from .metrics import iou as _iou, iou_from_counts
         L = L or self.learner
+        kw = {"views": views} if views else {}
         if self.device_metrics:
             if self._transductive:
-                masks, rows = L.mask_resident(list(test_idx), training=False, counts=True)
+                masks, rows = L.mask_resident(list(test_idx), training=False, counts=True, **kw)
             else:
                 masks, rows = [], []
                 for t in test_idx:
-                    m, r = L.mask_resident(list(train_idx) + [t], training=False, counts=True, last_only=True)
+                    m, r = L.mask_resident(list(train_idx) + [t], training=False, counts=True, last_only=True, **kw)
                     masks.append(m[-1])
                     rows.append(r[-1])
             ious = [iou_from_counts(r[0], r[1]) for r in rows]
         else:
-            preds = self._test_predictions(train_idx, test_idx, L)
+            preds = self._test_predictions(train_idx, test_idx, L, views)
             lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
             ious = [_iou(preds[j], lab[test_idx[j]]) for j in range(len(test_idx))]
             masks = [np.round(np.asarray(preds[j])[..., 1]).astype(bool) for j in range(len(test_idx))]

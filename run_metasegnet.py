@@ -20,6 +20,9 @@ every test image's predicted mask as DIR/<task>/sample<k>_query<j>_mask.png (wit
 --threshold-sweep [--threshold-sweep-val]: the final pass over the test (or val) tasks also reads back, per test image, a 2 x 256 histogram
 of its foreground probability by label class (csrc/sweep.hip) and writes the IoU at every threshold k/256, the best threshold and a
 reliability table to <checkpoint>/meta-<test|val>_threshold_sweep.json; what is predicted, printed and saved stays at 0.5.
+--eval-tta VIEW [VIEW ...] (hflip, vflip, hvflip): the final evaluation passes also predict every test batch mirrored and average the views'
+decoder-resolution logits on the device (csrc/tta.hip) before anything scores them; IoUs, results file, saved masks and sweep are those of
+the merged prediction.
 --resident-dataset: the tasks stay on the device as the bytes the dataset stores (4 per pixel, not 20); a task's shots are expanded on
 the device when it becomes resident (csrc/taskload.hip) -- and resampled to --image_size when the shards hold another size
 (--stored-image-size N).
@@ -41,8 +44,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from mliis_amd import checkpoint as ckpt  # noqa: E402
-from mliis_amd.args import (argument_parser, augment_mode, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler, model_kwargs,  # noqa: E402
-                            prediction_writer, stored_image_size, threshold_sweep, train_kwargs)
+from mliis_amd.args import (argument_parser, augment_mode, eval_views, evaluate_kwargs, hyper_search_kwargs, make_lr_scheduler,  # noqa: E402
+                            model_kwargs, prediction_writer, stored_image_size, threshold_sweep, train_kwargs)
 
 
 def _dataset(args, device, rank):
@@ -132,13 +135,15 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
     writer = prediction_writer(args)   # (the final passes only: not the search, the k-shot curves or the training above)
     if writer is not None:
         print("Saving predictions to {}".format(writer.directory))
+    views = eval_views(args)           # (--eval-tta: the same passes, and the validation pass of --threshold-sweep-val)
+    tta = {"eval_views": views} if views else {}
     mean_train_iou = None
     if train_set and not args.skip_train_task_eval:
         print("Evaluating {}-shot learning on training tasks.".format(args.shots))
         keep = ek["save_fine_tuned_checkpoints"]
         ek["save_fine_tuned_checkpoints"] = args.save_fine_tuned_checkpoints_train
         mean_train_iou, _ = evaluate_gecko(learner, train_set, lr_scheduler=lr_scheduler, serially_eval_all_tasks=False, lanes=lanes,
-                                           prediction_writer=writer, **ek)
+                                           prediction_writer=writer, **tta, **ek)
         ek["save_fine_tuned_checkpoints"] = keep
     name = "test"
     if args.eval_val_tasks:
@@ -152,7 +157,7 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
     print("Evaluating {}-shot learning on meta-{} tasks.".format(args.shots, name))
     mean_test_iou, task_name_iou_map = evaluate_gecko(learner, test_set, lr_scheduler=lr_scheduler, lanes=lanes, prediction_writer=writer,
                                                       serially_eval_all_tasks=args.serially_eval_all_test_tasks,
-                                                      **({"threshold_sweep": sweep} if sweep is not None else {}), **ek)
+                                                      **({"threshold_sweep": sweep} if sweep is not None else {}), **tta, **ek)
     print("Evaluated meta-{} tasks:".format(name))
     print(task_name_iou_map)
     if mean_train_iou is not None:
@@ -164,19 +169,22 @@ def _evaluate(args, learner, lr_scheduler, train_set, val_set, test_set, aug_poo
         json.dump(task_name_iou_map, f)
     print("Wrote results to {}".format(out))
     if sweep is not None:
-        _write_threshold_sweep(args, name, sweep, learner, lr_scheduler, val_set if sweep_on_val else None, lanes, ek)
+        _write_threshold_sweep(args, name, sweep, learner, lr_scheduler, val_set if sweep_on_val else None, lanes, dict(ek, **tta))
 
 
 def _write_threshold_sweep(args, name, sweep, learner, lr_scheduler, val_set, lanes, ek):
     """--threshold-sweep: <checkpoint>/meta-<test|val>_threshold_sweep.json from the final pass's sink (metrics.ThresholdSweep.summary:
     "iou_at_0.5" is the printed mean).  --threshold-sweep-val (val_set given): the same pass then runs over the validation tasks -- after the
     test pass, which has consumed the random state it always does -- and selected_on_val = the threshold that is best there, with the
-    test IoU at it (and the val curve it was read from).  The pass's own prints are dropped: the run's output stays that of a run without the flag."""
+    test IoU at it (and the val curve it was read from).  The pass's own prints are dropped: the run's output stays that of a run without the flag.
+    With --eval-tta (ek carries eval_views) both passes score the merged prediction and the file gains "tta_views"."""
     import contextlib
     import io
     from mliis_amd.eval import evaluate_gecko
     from mliis_amd.metrics import HIST_BINS, ThresholdSweep
     doc = sweep.summary()
+    if ek.get("eval_views"):
+        doc["tta_views"] = list(ek["eval_views"])
     if val_set is not None:
         on_val = ThresholdSweep()
         with contextlib.redirect_stdout(io.StringIO()):
@@ -199,6 +207,7 @@ def main(argv=None, learner_factory=None, device=None):
     args = argument_parser().parse_args(argv)
     stored_image_size(args)   # (a stored size other than --image_size without --resident-dataset is refused before anything is built)
     threshold_sweep(args)     # (... and so is a --threshold-sweep-val without validation tasks or with --eval_val_tasks)
+    views = eval_views(args)  # (... and an --eval-tta view given twice)
     random.seed(args.seed)
     aug_pool = None
     if args.augment and args.augment_on_host and args.augment_workers != 0:   # forked workers: created before anything initialises the GPU
@@ -238,6 +247,9 @@ def main(argv=None, learner_factory=None, device=None):
             lanes = [Learner(device=device, **dict(model_kwargs(args), seed=args.seed + 1000 * k), **rank_kw)
                      for k in range(1, args.concurrent_tasks)]
     print("Adapting tasks on {} learner(s).".format(1 + len(lanes)))
+    if views:   # (--eval-tta needs learners whose scoring methods merge views: refused here, before any training, not after it)
+        from mliis_amd.views import require_views_support
+        require_views_support([learner] + lanes, views)
 
     if args.restore_efficient_net_weights_from is not None and not args.pretrained:
         path = ckpt.latest_checkpoint(args.restore_efficient_net_weights_from)
