@@ -187,6 +187,18 @@ LOSS_SIGNATURES = {
     "mliis_head_focal_fused": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _sz, _p]),
 }
 
+# libmliis_region.so (include/mliis_region.h): the Tversky region term of the inner loop's loss on that pixel loss, a library of its own as
+# well; loaded only by a learner built with tversky=(alpha, beta)
+REGION_LIB_PATH = os.path.join(_HERE, "libmliis_region.so")
+REGION_SIGNATURES = {
+    "mliis_region_last_error": (C.c_char_p, []),
+    "mliis_tversky_ce_workspace_floats": (_sz, [_i, _i, _i]),
+    "mliis_tversky_ce": (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _sz, _p]),
+    "mliis_head_tversky_fused_supported": (_i, [_i, _i, _i, _i]),
+    "mliis_head_tversky_fused_workspace_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "mliis_head_tversky_fused": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _sz, _p]),
+}
+
 # libmliis_tta.so (include/mliis_tta.h): evaluation's flip test-time augmentation -- the mirrored copy of a batch and the merge of the views'
 # decoder-resolution logits, a library of its own as well; loaded only by an evaluation call with views= (--eval-tta)
 TTA_LIB_PATH = os.path.join(_HERE, "libmliis_tta.so")
@@ -204,7 +216,7 @@ class MliisError(RuntimeError):
 class _Lib:
     def __init__(self, path=None, signatures=None, last_error="mliis_last_error"):
         """Default: libmliis_hip.so at the module's LIB_PATH with SIGNATURES; (path, signatures, name of its error query): another
-        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib, sweep_lib, loss_lib, tta_lib)."""
+        library of the same conventions (score_lib, data_lib, steplog_lib, layerlog_lib, clip_lib, sweep_lib, loss_lib, tta_lib, region_lib)."""
         self._dll = None
         self._path, self._signatures, self._last_error = path, signatures, last_error
 
@@ -254,3 +266,4 @@ clip_lib = _Lib(CLIP_LIB_PATH, CLIP_SIGNATURES, "mliis_clip_last_error")
 sweep_lib = _Lib(SWEEP_LIB_PATH, SWEEP_SIGNATURES, "mliis_sweep_last_error")
 loss_lib = _Lib(LOSS_LIB_PATH, LOSS_SIGNATURES, "mliis_loss_last_error")
 tta_lib = _Lib(TTA_LIB_PATH, TTA_SIGNATURES, "mliis_tta_last_error")
+region_lib = _Lib(REGION_LIB_PATH, REGION_SIGNATURES, "mliis_region_last_error")

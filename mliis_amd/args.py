@@ -39,6 +39,28 @@ def _nonnegative_float(v) -> float:
     return f
 
 
+def _tversky_pair(t) -> tuple:
+    """(alpha, beta) of the Tversky index: two finite floats >= 0 whose sum is positive (ArgumentTypeError / ValueError otherwise)."""
+    try:
+        alpha, beta = t
+    except (TypeError, ValueError):
+        raise ValueError("tversky takes two numbers (alpha, beta), got {!r}".format(t)) from None
+    alpha, beta = _nonnegative_float(alpha), _nonnegative_float(beta)
+    if not alpha + beta > 0:
+        raise ValueError("tversky: alpha + beta must be positive, got {!r}".format(t))
+    return alpha, beta
+
+
+class _TverskyPair(argparse.Action):
+    """--tversky ALPHA BETA: the values pass _nonnegative_float one by one; the pair is refused here when both are zero."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        try:
+            setattr(namespace, self.dest, _tversky_pair(values))
+        except (ValueError, argparse.ArgumentTypeError) as e:
+            parser.error("argument {}: {}".format(option_string, e))
+
+
 _FLAGS = [
     ("--fine-tune-task", dict(type=str, default=None)),
     ("--fine-tuned-checkpoint", dict(type=str, default=None)),
@@ -208,6 +230,15 @@ _EXT = [
                          help="weight of the foreground pixels in the inner loop's pixel loss: a pixel counts 1 + (W - 1) * label.  The sum is "
                               "still divided by N H W, not by the sum of the weights, so W > 1 raises the loss scale and usually wants a "
                               "smaller --learning-rate or a clip.  The same kernels and places as --focal-gamma")),
+    ("--tversky", dict(nargs=2, type=_nonnegative_float, action=_TverskyPair, default=None, metavar=("ALPHA", "BETA"),
+                       help="Tversky region term in the inner loop's loss, on the device (csrc/tversky.hip): -ln(2T / (T + 1)) with T the "
+                            "batch mean of (I + eps) / (I + ALPHA * FP + BETA * FN + eps) on the foreground probability, added to the "
+                            "pixel term whatever --loss_name says.  1 1 is the soft IoU of --loss_name bce_dice, 0.5 0.5 the soft Dice "
+                            "coefficient; BETA > ALPHA weighs a missed foreground pixel more than a false alarm.  Both >= 0, not both 0.  "
+                            "The step's tail stays on the decoder's map (three launches, no full-resolution tensor).  Composes with "
+                            "--focal-gamma, --fg-weight, --label_smoothing, --l2, --l1 and --darc1; applies wherever a model is adapted "
+                            "(the same places as --inner-clip-norm); evaluation and prediction are unchanged.  `iou` in "
+                            "inner_loop.jsonl stays the soft IoU")),
     ("--threshold-sweep", dict(action="store_true",
                                help="sweep the decision threshold in the final evaluation pass over the meta-test (or, with "
                                     "--eval_val_tasks, meta-val) tasks: every test image leaves a 2 x 256 histogram of its foreground "
@@ -255,6 +286,14 @@ def focal_loss(a) -> dict:
     if w is not None:
         out["fg_weight"] = _positive_float(w)
     return out
+
+
+def tversky(a) -> dict:
+    """The `tversky` argument of the Learner from --tversky ALPHA BETA: absent without the flag."""
+    t = getattr(a, "tversky", None)
+    if t is None:
+        return {}
+    return dict(tversky=_tversky_pair(t))
 
 
 def threshold_sweep(a):
@@ -337,6 +376,7 @@ def model_kwargs(a) -> dict:
     if clip is not None:   # (absent without the flags as well; its ring holds the steps of one task like the step log's)
         log.update(grad_clip=clip, clip_log=capacity_for(steps))
     log.update(focal_loss(a))   # (absent without the flags as well)
+    log.update(tversky(a))      # (likewise)
     return dict(feature_extractor_name=a.feature_extractor_name, image_size=a.image_size, rsd=a.rsd or None,
                 learning_rate=a.learning_rate, optimizer="sgd" if a.sgd else "adam", l2=a.l2, l1=a.l1, darc1=a.darc1,
                 dice=("dice" in a.loss_name), label_smoothing=a.label_smoothing, final_layer_dropout_rate=a.final_layer_dropout_rate,

@@ -1,7 +1,10 @@
 // The pixel-loss kernels of the decoder tail, once for every loss: the geometry of the partial-sum grid and of the fused head's tiles, the
 // workspace sizes, the fold of the loss partials, and the three kernel bodies -- partial sums, gradient, fused head tile -- as templates
 // over a per-pixel policy.  head.hip (softmax cross-entropy: CePixel, libmliis_hip.so) and focal.hip (the focal, foreground-weighted loss:
-// FocalPixel of focal_math.hpp, libmliis_loss.so) instantiate them behind their own __global__ kernels and entry points.
+// FocalPixel of focal_math.hpp, libmliis_loss.so) instantiate them behind their own __global__ kernels and entry points.  tversky.hip (the
+// Tversky region term, libmliis_region.so) runs the same bodies through their hooks: a region term for the fold (JaccardRegion is the
+// default: the soft IoU's dice term), a region gradient for the gradient pass and the fused head's tiles (JaccardGrad / NoRegion), and a
+// logits source for the partial-sum pass (LoadedLogits).
 //
 // A policy is a small struct of the loss's scalars, passed by value.  Per pixel, from the two logits zz and the two stored labels tt:
 //   auto a = px.at(zz, tt);             what the pixel's gradient and loss terms share, with the softmax pair a.p0, a.p1
@@ -9,6 +12,8 @@
 //   g = px.with_dice(g, dp1);           the dice term's d / dz1 added to that pair (the gradient pass only; dp1 is 0 without the term)
 //   px.terms(a, l, I, Sp, St);          adds the pixel's {loss term, p1 y1, p1, y1} to the four sums
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "head_math.hpp"
 
@@ -73,13 +78,29 @@ __device__ __forceinline__ void store_partials(float l, float I, float Sp, float
   if (threadIdx.x < 4) dst[threadIdx.x] = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
 }
 
-// out: [0] loss, [1] pixel loss, [2] iou ; coef[n] = {A_n, B_n} for the dice gradient (0 when dice off).  One block: 8 images at a time,
-// 32 lanes per image fold that image's partial blocks (double precision), a lane butterfly finishes the image, thread 0 adds the
+// The region term of the fold.  image(): from an image's three sums, its index T_n (returned: the term is -ln(2 T / (T + 1)) on the batch
+// mean T) and, into coef[n], the pair {1 / D_n, (I + eps) / D_n^2} of its denominator that the fold scales by (dL/dT) / N into coef[n].  kIndices = 1: T_n is the
+// soft IoU that out[2] reports anyway; 2: the fold keeps the two means apart.  JaccardRegion is the dice term of the reference.
+struct JaccardRegion {
+  static constexpr int kIndices = 1;
+  int on;
+  __device__ __forceinline__ double image(double I, double Sp, double St, double iou_n, float* __restrict__ coef, int n) const {
+    const double eps = 1e-7;
+    const double U = Sp + St - I;
+    coef[2 * n + 0] = (float)(1.0 / (U + eps));
+    coef[2 * n + 1] = (float)((I + eps) / ((U + eps) * (U + eps)));
+    return iou_n;
+  }
+};
+
+// out: [0] loss, [1] pixel loss, [2] iou ; coef[n] = {A_n, B_n} for the region gradient (0 when the term is off).  One block: 8 images at
+// a time, 32 lanes per image fold that image's partial blocks (double precision), a lane butterfly finishes the image, thread 0 adds the
 // images up in index order (fixed order: deterministic).
-__device__ __forceinline__ void loss_fold(const float* __restrict__ part, int nblk, int N, int HW, int dice, float extra_loss,
-                                          float* __restrict__ out, float* __restrict__ coef) {
-  __shared__ double s_l[8], s_iou[8];
-  double l = 0.0, iou = 0.0;
+template <class Region>
+__device__ __forceinline__ void loss_fold_with(Region rg, const float* __restrict__ part, int nblk, int N, int HW, float extra_loss,
+                                               float* __restrict__ out, float* __restrict__ coef) {
+  __shared__ double s_l[8], s_iou[8 * Region::kIndices];
+  double l = 0.0, iou = 0.0, tv = 0.0;
   const double eps = 1e-7;
   const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
   for (int n0 = 0; n0 < N; n0 += 8) {
@@ -102,63 +123,91 @@ __device__ __forceinline__ void loss_fold(const float* __restrict__ part, int nb
       const double U = Sp + St - I;
       s_l[g] = v[0];
       s_iou[g] = (I + eps) / (U + eps);
-      coef[2 * n + 0] = (float)(1.0 / (U + eps));
-      coef[2 * n + 1] = (float)((I + eps) / ((U + eps) * (U + eps)));
+      const double T = rg.image(I, Sp, St, (I + eps) / (U + eps), coef, n);
+      if constexpr (Region::kIndices == 2) s_iou[8 + g] = T;
     }
     __syncthreads();
     if (threadIdx.x == 0)
       for (int j = 0; j < 8 && n0 + j < N; ++j) {
         l += s_l[j];
         iou += s_iou[j];
+        if constexpr (Region::kIndices == 2) tv += s_iou[8 + j];
       }
     __syncthreads();
   }
   if (threadIdx.x != 0) return;
   l /= (double)N * HW;
   iou /= N;
+  const double T = Region::kIndices == 2 ? tv / N : iou;
   double loss = l + extra_loss;
-  double dLdiou = 0.0;
-  if (dice) {
-    loss -= log(2.0 * iou / (iou + 1.0));
-    dLdiou = -1.0 / (iou * (iou + 1.0));
+  double dLdT = 0.0;
+  if (rg.on) {
+    loss -= log(2.0 * T / (T + 1.0));
+    dLdT = -1.0 / (T * (T + 1.0));
   }
   for (int n = 0; n < N; ++n) {
-    coef[2 * n + 0] = (float)(coef[2 * n + 0] * dLdiou / N);
-    coef[2 * n + 1] = (float)(coef[2 * n + 1] * dLdiou / N);
+    coef[2 * n + 0] = (float)(coef[2 * n + 0] * dLdT / N);
+    coef[2 * n + 1] = (float)(coef[2 * n + 1] * dLdT / N);
   }
   out[0] = (float)loss;
   out[1] = (float)l;
   out[2] = (float)iou;
 }
+__device__ __forceinline__ void loss_fold(const float* __restrict__ part, int nblk, int N, int HW, int dice, float extra_loss,
+                                          float* __restrict__ out, float* __restrict__ coef) {
+  loss_fold_with(JaccardRegion{dice}, part, nblk, N, HW, extra_loss, out, coef);
+}
 
 // ------------------------------------------------------------------------------------------------ the chain: partial sums, gradient
-// part layout [n][blk][4] (store_partials); grid (part_blocks(HW), N)
-template <class Pixel>
-__device__ __forceinline__ void loss_partial(Pixel px, const float* __restrict__ logits, const float* __restrict__ labels,
-                                             const int* __restrict__ idx, int HW, float* __restrict__ part) {
+// part layout [n][blk][4] (store_partials); grid (part_blocks(HW), N).  The logits of image n's pixel p come from a source: LoadedLogits reads
+// them, a caller's own source may form them (tversky.hip rebuilds them from the decoder's map).
+struct LoadedLogits {
+  const float* logits;   // [N][HW][2]
+  int HW;
+  struct Image {
+    const float* z;
+    __device__ __forceinline__ float2 operator()(int p) const { return *reinterpret_cast<const float2*>(z + (long long)p * 2); }
+  };
+  __device__ __forceinline__ Image image(int n) const { return Image{logits + (long long)n * HW * 2}; }
+};
+template <class Pixel, class Logits>
+__device__ __forceinline__ void loss_partial_from(Pixel px, Logits zsrc, const float* __restrict__ labels, const int* __restrict__ idx, int HW,
+                                                  float* __restrict__ part) {
   __shared__ float sm[4][4];
   const int n = blockIdx.y;
   const int src = idx ? idx[n] : n;
-  const float* z = logits + (long long)n * HW * 2;
+  const auto z = zsrc.image(n);
   const float* t = labels + (long long)src * HW * 2;
   const unsigned nblk = gridDim.x;
   float l = 0.f, I = 0.f, Sp = 0.f, St = 0.f;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += nblk * 256) {
-    const float2 zz = *reinterpret_cast<const float2*>(z + (long long)p * 2);
+    const float2 zz = z(p);
     const float2 tt = *reinterpret_cast<const float2*>(t + (long long)p * 2);
     px.terms(px.at(zz, tt), l, I, Sp, St);
   }
   store_partials(l, I, Sp, St, sm, part + ((long long)n * nblk + blockIdx.x) * 4);
 }
+template <class Pixel>
+__device__ __forceinline__ void loss_partial(Pixel px, const float* __restrict__ logits, const float* __restrict__ labels,
+                                             const int* __restrict__ idx, int HW, float* __restrict__ part) {
+  loss_partial_from(px, LoadedLogits{logits, HW}, labels, idx, HW, part);
+}
+
+// The region term's d / dz1 at a pixel from the image's pair coef[n] = {An, Bn} (the fold's), the stored foreground label and p1.
+// A functor float(An, Bn, y1, p1).  JaccardGrad names the dice term's, which loss_grad spells itself (through a functor the compiler
+// schedules focal_grad_k's instructions in another order); NoRegion marks a fused head without a region term (its tiles add the loss
+// terms instead).
+struct JaccardGrad {};
+struct NoRegion {};
 
 // dlogits (nullable) = the pixel's gradient with the dice term's (coef, from the fold); pred (nullable) = (softmax > 0.5) as float.
 // fin_part != nullptr (no dice term: the gradient needs nothing from the fold): workgroup (0, 0) also folds the loss partials into
 // fin_out[] before its share of the gradient -- one launch fewer than partial -> fold -> gradient.  One pixel per thread.
-template <class Pixel>
+template <class Pixel, class RegionGrad = JaccardGrad>
 __device__ __forceinline__ void loss_grad(Pixel px, const float* __restrict__ logits, const float* __restrict__ labels,
                                           const int* __restrict__ idx, int HW, const float* __restrict__ coef, float* __restrict__ dlogits,
                                           float* __restrict__ pred, const float* __restrict__ fin_part, int fin_nblk, int N, float extra_loss,
-                                          float* __restrict__ fin_out, float* __restrict__ fin_coef) {
+                                          float* __restrict__ fin_out, float* __restrict__ fin_coef, RegionGrad region = RegionGrad{}) {
   if (fin_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) loss_fold(fin_part, fin_nblk, N, HW, 0, extra_loss, fin_out, fin_coef);   // (uniform)
   const int n = blockIdx.y;
   const int src = idx ? idx[n] : n;
@@ -169,7 +218,11 @@ __device__ __forceinline__ void loss_grad(Pixel px, const float* __restrict__ lo
     const float2 zz = *reinterpret_cast<const float2*>(z + (long long)p * 2);
     const float2 tt = *reinterpret_cast<const float2*>(t + (long long)p * 2);
     const auto a = px.at(zz, tt);
-    const float dp1 = (An * tt.y - Bn * (1.f - tt.y)) * a.p1 * (1.f - a.p1);
+    float dp1;
+    if constexpr (std::is_same<RegionGrad, JaccardGrad>::value)
+      dp1 = (An * tt.y - Bn * (1.f - tt.y)) * a.p1 * (1.f - a.p1);
+    else
+      dp1 = region(An, Bn, tt.y, a.p1);
     const float2 g = px.with_dice(px.grad(a), dp1);
     if (dlogits) *reinterpret_cast<float2*>(dlogits + ((long long)n * HW + p) * 2) = g;
     if (pred) *reinterpret_cast<float2*>(pred + ((long long)n * HW + p) * 2) = make_float2(a.p0 > 0.5f ? 1.f : 0.f, a.p1 > 0.5f ? 1.f : 0.f);
@@ -190,10 +243,14 @@ __device__ __forceinline__ void loss_grad(Pixel px, const float* __restrict__ lo
 // write back and invalidate a whole L2 each (measured: 39 us for the launch, more than the four it replaces).  (A first form without
 // the LDS phase -- every decoder pixel rebuilding its ~100 candidates itself -- took 69 us: one dependent load chain per candidate.)
 // grid (head_tiles(Hi) * tiles_x, N); the host admits only maps with head_fused_supported(Hi, Wi, Ho, Wo).
-template <class Pixel>
+// With a region gradient (Region != NoRegion: the second pass of a two-pass head, after the sums and their fold) phase 1 adds the region
+// term's d / dz1 from coef[n] to the entry and no loss terms are formed; part is not written.
+template <class Pixel, class Region = NoRegion>
 __device__ __forceinline__ void head_fused_tile(Pixel px, const float* __restrict__ small, const float* __restrict__ labels,
                                                 const int* __restrict__ idx, int Hi, int Wi, int Ho, int Wo, float sh, float sw,
-                                                float* __restrict__ dsmall, float* __restrict__ part, int tiles_x) {
+                                                float* __restrict__ dsmall, float* __restrict__ part, int tiles_x,
+                                                const float* __restrict__ coef = nullptr, Region region = Region{}) {
+  constexpr bool kRegion = !std::is_same<Region, NoRegion>::value;
   __shared__ float2 gl[kHeadFoot * kHeadFoot];
   __shared__ float sm[4][4];
   const int t = threadIdx.x;
@@ -218,8 +275,12 @@ __device__ __forceinline__ void head_fused_tile(Pixel px, const float* __restric
     const float2 zz = bilinear_sample<float2>(zb, Wi, 2, y0, y1, x0, x1, ly, lx);   // (resize_fwd_k's arithmetic)
     const float2 tt = *reinterpret_cast<const float2*>(tb + ((long long)ho * Wo + wo) * 2);
     const auto a = px.at(zz, tt);
-    gl[fr * kHeadFoot + fc] = px.grad(a);
-    if (y0 >= hi0 && y0 <= hi1 && x0 >= wi0 && x0 <= wi1) px.terms(a, l, I, Sp, St);   // this tile owns the image pixel's loss terms
+    if constexpr (kRegion) {
+      gl[fr * kHeadFoot + fc] = px.with_dice(px.grad(a), region(coef[2 * n], coef[2 * n + 1], tt.y, a.p1));
+    } else {
+      gl[fr * kHeadFoot + fc] = px.grad(a);
+      if (y0 >= hi0 && y0 <= hi1 && x0 >= wi0 && x0 <= wi1) px.terms(a, l, I, Sp, St);   // this tile owns the image pixel's loss terms
+    }
   }
   __syncthreads();
 #pragma unroll
@@ -252,7 +313,7 @@ __device__ __forceinline__ void head_fused_tile(Pixel px, const float* __restric
     }
     if (live && rl == 0) *reinterpret_cast<float2*>(dsmall + ((long long)n * Hi * Wi + (long long)hi * Wi + wi) * 2) = acc;
   }
-  store_partials(l, I, Sp, St, sm, part + ((long long)n * gridDim.x + blockIdx.x) * 4);
+  if constexpr (!kRegion) store_partials(l, I, Sp, St, sm, part + ((long long)n * gridDim.x + blockIdx.x) * 4);
 }
 
 }  // namespace mliis

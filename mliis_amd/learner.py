@@ -32,7 +32,7 @@ import torch
 from . import ops, spec
 from . import clip as clip_mod
 from . import layerlog
-from ._lib import MliisError, clip_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib
+from ._lib import MliisError, clip_lib, layerlog_lib, lib, loss_lib, region_lib, score_lib, steplog_lib, sweep_lib
 from .arena import Arena
 from .metrics import unpack_mask
 from .passes import _Passes
@@ -57,7 +57,7 @@ class Learner(_Passes):
                  device="cuda:0", use_graph: bool = True, max_shots: int = 16, matmul_precision: str = "fp32",
                  small_fused: Optional[bool] = None, dw_march: Optional[bool] = None, fuse_bn2: Optional[bool] = None, fuse_head: Optional[bool] = None,
                  augment_batch_capacity: int = 0, rng_stream: int = 0, step_log: int = 0, layer_log: bool = False, grad_clip=None, clip_log: int = 0,
-                 focal_gamma: float = 0.0, fg_weight: float = 1.0):
+                 focal_gamma: float = 0.0, fg_weight: float = 1.0, tversky=None):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam' (Adam with beta1=0, the reference default)")
         if not torch.cuda.is_available():
@@ -76,6 +76,21 @@ class Learner(_Passes):
         self.focal = self.focal_gamma != 0.0 or self.fg_weight != 1.0
         if self.focal:
             loss_lib.load()
+        # tversky = (alpha, beta), both >= 0 and not both 0: the loss gains the region term -ln(2T / (T + 1)), T the batch mean of the Tversky
+        # index (I + eps) / (I + alpha FP + beta FN + eps) on the channel-1 probability (include/mliis_region.h), whatever `dice` says --
+        # (1, 1) is the dice term -- on the pixel term above: ops.head_tversky_fused / ops.tversky_ce where the step issues the heads and
+        # chains above.  The library is loaded here; the pair is by-value kernel arguments, captured into the step's graph.  None (the
+        # default): nothing is loaded or allocated and the step's launches are what they were.
+        self.tversky = None
+        if tversky is not None:
+            try:
+                alpha, beta = (float(v) for v in tversky)
+            except (TypeError, ValueError):
+                raise ValueError("tversky must be a pair (alpha, beta) of floats, got {!r}".format(tversky)) from None
+            if not (math.isfinite(alpha) and math.isfinite(beta) and alpha >= 0.0 and beta >= 0.0 and alpha + beta > 0.0):
+                raise ValueError("tversky needs finite alpha, beta >= 0 with alpha + beta > 0, got {!r}".format(tversky))
+            self.tversky = (alpha, beta)
+            region_lib.load()
         # operand precision of the matrix cores in the dense convs: "fp32" (BASELINE configs 1-3) or "bf16" (operands rounded to bf16 on
         # the fly, fp32 accumulation; everything else stays fp32).  Passed with every dense-conv call (nothing process-wide).
         # "bf16-storage" (BASELINE configs[3]): bf16 operands AND the expanded tensors of the MBConv blocks (z0, z1, a1 and their
@@ -596,12 +611,20 @@ class Learner(_Passes):
         # softmax cross-entropy, its gradient, the resize's transpose -- is ONE launch on the decoder's map (ops.head_ce_fused)
         hd_, H_ = self.arch.h_dec, self.arch.image_size
         hlib, hname = (loss_lib, "mliis_head_focal_fused") if self.focal else (lib, "mliis_head_ce_fused")
-        head_fused = bool(self.fuse_head and not self.dice and not self.darc1 and hlib.size(hname + "_supported", hd_, hd_, H_, H_))
+        if self.tversky is not None:   # (the region term is the head's own second pass: `dice` does not keep it off the decoder's map)
+            hlib, hname = region_lib, "mliis_head_tversky_fused"
+        head_fused = bool(self.fuse_head and (self.tversky is not None or not self.dice) and not self.darc1 and
+                          hlib.size(hname + "_supported", hd_, hd_, H_, H_))
         logits = self._forward(P, self.shots_x, P.idx, True, upsample=not head_fused)
         if head_fused:
             if P.head_ws is None:
-                P.head_ws = ops.Workspace(self.device, hlib.size(hname + "_workspace_floats", P.N, hd_, hd_))
-            if self.focal:   # TWO launches: the focal head and its own fold (the other library's backward-data launch cannot fold for it)
+                wdims = (P.N, hd_, hd_, H_, H_) if self.tversky is not None else (P.N, hd_, hd_)
+                P.head_ws = ops.Workspace(self.device, hlib.size(hname + "_workspace_floats", *wdims))
+            if self.tversky is not None:   # THREE launches on the decoder's map: the sums, their fold, the gradient tiles
+                ops.head_tversky_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, self.focal_gamma, self.fg_weight,
+                                       self.tversky[0], self.tversky[1], P.dsmall, P.loss_out, ws=P.head_ws)
+                P.head_fin = None
+            elif self.focal:   # TWO launches: the focal head and its own fold (the other library's backward-data launch cannot fold for it)
                 ops.head_focal_fused(P.small, self.shots_y, P.idx, (H_, H_), self.label_smoothing, self.focal_gamma, self.fg_weight, P.dsmall,
                                      P.loss_out, ws=P.head_ws)
                 P.head_fin = None
@@ -610,7 +633,10 @@ class Learner(_Passes):
                                               finalize=False)
                 P.head_fin = (buf, (H_, H_), 0.0, P.loss_out)
         else:
-            if self.focal:
+            if self.tversky is not None:
+                ops.tversky_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.focal_gamma, self.fg_weight, self.tversky[0], self.tversky[1],
+                               0.0, want_grad=True, dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
+            elif self.focal:
                 ops.focal_ce(logits, self.shots_y, P.idx, self.label_smoothing, self.focal_gamma, self.fg_weight, self.dice, 0.0, want_grad=True,
                              dlogits=P.dlogits, out=P.loss_out, ws=self.ws)
             else:

@@ -17,7 +17,7 @@ import torch
 
 from . import clip as _clip
 from . import layerlog as _layerlog
-from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, loss_lib, score_lib, steplog_lib, sweep_lib, tta_lib
+from ._lib import MliisError, clip_lib, data_lib, layerlog_lib, lib, loss_lib, region_lib, score_lib, steplog_lib, sweep_lib, tta_lib
 from .spec import BN_EPS, BN_MOMENTUM, MEAN_RGB, STDDEV_RGB
 
 _MEAN3 = (C.c_float * 3)(*MEAN_RGB)
@@ -1320,6 +1320,44 @@ def head_focal_fused(small, labels, idx, size, label_smoothing, gamma, fg_weight
     _timed("head_focal_fused", {}, lambda: loss_lib.call("mliis_head_focal_fused", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd, Wd,
                                                          int(size[0]), int(size[1]), float(label_smoothing), float(gamma), float(fg_weight),
                                                          float(extra_loss), _ptr(_chk(dsmall)), _ptr(_chk(out)), _ptr(buf), buf.numel(), _stream()))
+    return out, dsmall
+
+
+def tversky_ce(logits, labels, idx=None, label_smoothing=0.0, gamma=0.0, fg_weight=1.0, alpha=1.0, beta=1.0, extra_loss=0.0, want_grad=True,
+               dlogits=None, out=None, ws: Optional[Workspace] = None):
+    """focal_ce's counterpart with the Tversky region term (libmliis_region.so, include/mliis_region.h, csrc/tversky.hip): the pixel term
+    of focal_ce (gamma = 0, fg_weight = 1: the cross-entropy) minus ln(2T / (T + 1)), T the batch mean of (I + eps) / (I + alpha FP +
+    beta FN + eps); alpha = beta = 1 is the dice term.  out[0..2] = {loss, the pixel term, the soft IoU}; dlogits as there."""
+    N, H, W, _ = logits.shape
+    dev = logits.device
+    _dense(logits, labels, idx)
+    _out_dense(dlogits, tuple(logits.shape), what="tversky_ce dlogits")
+    if want_grad and dlogits is None:
+        dlogits = torch.empty_like(logits)
+    out = torch.empty(4, dtype=torch.float32, device=dev) if out is None else out
+    ws = ws or default_ws()
+    buf = ws.get(region_lib.size("mliis_tversky_ce_workspace_floats", N, H, W))
+    _timed("tversky_ce", {}, lambda: region_lib.call("mliis_tversky_ce", _ptr(_chk(logits)), _ptr(_chk(labels)), _ptr(idx), N, H, W,
+                                                     float(label_smoothing), float(gamma), float(fg_weight), float(alpha), float(beta),
+                                                     float(extra_loss), _ptr(dlogits) if want_grad else None, _ptr(_chk(out)), _ptr(buf),
+                                                     buf.numel(), _stream()))
+    return out, dlogits
+
+
+def head_tversky_fused(small, labels, idx, size, label_smoothing, gamma, fg_weight, alpha, beta, dsmall, out, extra_loss=0.0,
+                       ws: Optional[Workspace] = None):
+    """head_focal_fused's counterpart for the same loss: resize(small -> size) -> tversky_ce -> gradient -> resize^T on the decoder's map,
+    three launches (the images' sums, their fold, the gradient tiles; the full-resolution logits are never written): dsmall and
+    out[0..2] = {loss, the pixel term, the soft IoU}."""
+    N, Hd, Wd, _ = small.shape
+    _dense(small, labels, idx)
+    _out_dense(dsmall, tuple(small.shape), what="head_tversky_fused dsmall")
+    ws = ws or default_ws()
+    buf = ws.get(region_lib.size("mliis_head_tversky_fused_workspace_floats", N, Hd, Wd, int(size[0]), int(size[1])))
+    _timed("head_tversky_fused", {}, lambda: region_lib.call("mliis_head_tversky_fused", _ptr(_chk(small)), _ptr(_chk(labels)), _ptr(idx), N, Hd,
+                                                             Wd, int(size[0]), int(size[1]), float(label_smoothing), float(gamma),
+                                                             float(fg_weight), float(alpha), float(beta), float(extra_loss),
+                                                             _ptr(_chk(dsmall)), _ptr(_chk(out)), _ptr(buf), buf.numel(), _stream()))
     return out, dsmall
 
 
